@@ -7,16 +7,23 @@ code/run_styledmnist_downstream_expr.py:231-238), fp32, one fused HIP training s
 (forward, ELBO, 2 contrastive terms, backward, Adam) through CLEARVAETrainer's engine.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config mnist|celeba-mim|celeba|camelyon-bf16]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line with the headline figure
+(`value` images/s, `ms_per_step`).  --dump-outputs DIR then writes what the last timed step left with its
+caller as DIR/<name>.npy (dump_outputs below): weights, batches and noise are seeded, so two builds run with
+the same arguments can be compared array for array.  Everything under "After the timed region" below, the
+extra workloads and keys of the default config and the exposed all-reduce time run only with --full.
 
 --gpus N > 1: one process per GPU over RCCL.  Run directly, bench.py starts `torch.distributed.run
 --nproc-per-node N` as a child process (before any GPU call) and passes its exit status on; under an
 external torch.distributed.run WORLD_SIZE must equal N.  Per-GPU batch fixed (weak scaling); value = images
 processed by all ranks / max-over-ranks wall time.  CV_DIST_BACKEND=gloo rehearses the flow with all ranks on
-one GPU.  The default config also times, at every N, the weak-scaling keys "celeba" (VAE64 CLEAR-VAE fp32,
-256 per GPU: north_star's scaling target), "pacs" (32 per GPU: configs[3] at N=4) and "camelyon_bf16" (128
-per GPU bf16: configs[4] at N=8), each with the exposed all-reduce time per step at N > 1.
+one GPU.  With --full the default config also times, at every N, the weak-scaling keys "celeba" (VAE64
+CLEAR-VAE fp32, 256 per GPU: north_star's scaling target), "pacs" (32 per GPU: configs[3] at N=4) and
+"camelyon_bf16" (128 per GPU bf16: configs[4] at N=8), each with the exposed all-reduce time per step at N > 1.
 
-After the timed region (nothing below is inside it):
+After the timed region, with --full (nothing below is inside it):
   (1) an in-step pass: the step's programs are enqueued eagerly behind a spin kernel long enough for the
       host to queue the whole step, with a HIP timing-event pair around every call on the step's stream
       (single-stream schedule), so each call's time is its duration inside a real step; the roofline is
@@ -532,8 +539,11 @@ def step_error(cfg, device):
     return out
 
 
-def run_workload(name, cfg, steps, warmup, device, world, rank, detail=True, kernel_table=None):
-    """Time `steps` fused steps of configuration `cfg` (after `warmup`), then the in-step pass."""
+def run_workload(name, cfg, steps, warmup, device, world, rank, detail=True, kernel_table=None, comm=True,
+                 keep_outputs=False):
+    """Time `steps` fused steps of configuration `cfg` (after `warmup`), then the in-step pass (detail) and, at
+    N > 1, the exposed all-reduce pass (comm).  keep_outputs: res["outputs"] holds what the last timed step
+    returned and the parameters it left (copied after the timed region)."""
     from cvhip.engine import ClearStep
 
     arch, z, C, hw, B, mode, nl, hp, est = cfg
@@ -559,8 +569,9 @@ def run_workload(name, cfg, steps, warmup, device, world, rank, detail=True, ker
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for i in range(steps):
-        step(warmup + i)
+        last = step(warmup + i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -576,7 +587,9 @@ def run_workload(name, cfg, steps, warmup, device, world, rank, detail=True, ker
     res = {"value": value, "el": el, "ms_per_step": el / max(steps, 1) * 1e3, "finite": finite, "eng": eng,
            "algorithmic_tflops": step_flops_per_image(eng.spec, mode) * value / 1e12,
            "executed_tflops": executed_flops_per_image(eng.spec, mode) * value / 1e12}
-    if world > 1:
+    if keep_outputs and last is not None:  # (before any later pass steps the model again)
+        res["outputs"] = step_outputs(tr, last)
+    if world > 1 and comm:
         res["comm"] = comm_pass(eng, step, warmup + steps, device)
     if detail:
         G = eng.graphs[B]
@@ -594,6 +607,43 @@ def run_workload(name, cfg, steps, warmup, device, world, rank, detail=True, ker
                              f"{fl / (ms * 1e-3) / 1e12:12.2f}\n")
                 fh.write(f"{'total (sum of calls)':60s} {sum(instep.values()):11.4f} {sum(iso.values()):9.4f}\n")
     return res
+
+
+def step_outputs(tr, ret):
+    """What a caller of the step holds after it: the loss vector the step returned (CLEAR-MIM: and the 5
+    estimator-learning losses) and the parameters and buffers of the networks it updated, as host copies."""
+    out = {}
+    if isinstance(ret, tuple):
+        out["losses"], out["learn_losses"] = ret[0], ret[1]
+    else:
+        out["losses"] = ret
+    nets = [("model", tr.model)]
+    if getattr(tr, "mi_estimator", None) is not None:
+        nets.append(("mi_estimator", tr.mi_estimator))
+    for prefix, net in nets:
+        for k, v in net.state_dict().items():
+            out[f"{prefix}.{k}"] = v
+    return {k: v.detach().cpu().clone() for k, v in out.items()}
+
+
+DUMP_BYTES = 60 << 20  # of array data in all (the .npy headers stay well inside the 64 MB a dump may take)
+
+
+def dump_outputs(outputs, path):
+    """Write each output as path/<name>.npy: float32 (float64 for integer and double tensors), flattened.  An
+    array above its equal share of DUMP_BYTES is cut to a fixed sample: indices drawn once from seed 0 by its
+    size, sorted, so every run and every build keeps the same elements."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(outputs), 1)
+    for name, t in outputs.items():
+        wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+        a = t.to(torch.float64 if wide else torch.float32).reshape(-1).numpy()
+        keep = share // a.itemsize
+        if a.size > keep:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def comm_pass(eng, step, i0, device, k=10):
@@ -732,6 +782,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="mnist", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the config's)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: in-step pass and roofline, CPU baselines, "
+                         "step error against the CPU reference, the other configs' keys, the input pipeline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-pass", action="store_true", help="skip the in-step pass (profiling runs)")
     ap.add_argument("--no-c3", action="store_true", help="default config: skip the configs[2] extra keys")
@@ -745,6 +800,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch check without a GPU: the ranks join a gloo group and rank 0 prints the world")
     args = ap.parse_args()
+    if args.kernel_table and not args.full:
+        ap.error("--kernel-table needs --full (the table comes from the in-step pass)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # one process per GPU: start torch.distributed.run as a child process before anything touches the GPU
@@ -815,14 +872,18 @@ def main():
                 print(json.dumps({"label": label, "lane": c[3], "kernels": call_kernels(G, label)}))
         return
 
-    res = run_workload(args.config, cfg, args.steps, args.warmup, device, world, rank,
-                       detail=not args.no_kernel_pass, kernel_table=args.kernel_table)
+    detail = args.full and not args.no_kernel_pass
+    res = run_workload(args.config, cfg, args.steps, args.warmup, device, world, rank, detail=detail,
+                       kernel_table=args.kernel_table, comm=args.full,
+                       keep_outputs=args.dump_outputs is not None and rank == 0)
+    if "outputs" in res:
+        dump_outputs(res.pop("outputs"), args.dump_outputs)
     c3 = None
-    extra = args.config == "mnist" and not args.no_c3 and args.batch is None
+    extra = args.full and args.config == "mnist" and not args.no_c3 and args.batch is None
     if extra and world == 1:
         ccfg = CONFIGS["celeba-mim"]
         k3 = min(args.steps, 60)
-        r3 = run_workload("celeba-mim", ccfg, k3, 5, device, 1, 0, detail=not args.no_kernel_pass)
+        r3 = run_workload("celeba-mim", ccfg, k3, 5, device, 1, 0, detail=detail)
         c3 = {"metric": "training images/sec (configs[2])", "value": round(r3["value"], 1), "unit": "images/s",
               "ms_per_step": round(r3["ms_per_step"], 4), "steps": k3, "warmup": 5, "dtype": "fp32",
               "config": workload_label("celeba-mim", ccfg, 1),
@@ -838,8 +899,7 @@ def main():
         for key, cname, bs in SCALING_KEYS:
             ccfg = CONFIGS[cname]
             assert ccfg[4] == bs, (cname, ccfg[4])
-            scaling[key] = scaling_entry(cname, ccfg, min(args.steps, 100), device, world, rank,
-                                         detail=not args.no_kernel_pass)
+            scaling[key] = scaling_entry(cname, ccfg, min(args.steps, 100), device, world, rank, detail=detail)
         if world == 1:  # (configs[4]'s shard in fp32 beside the bf16 key: their ratio is the bf16 speed-up)
             scaling["camelyon_fp32"] = scaling_entry("camelyon-fp32", CONFIGS["camelyon-fp32"], min(args.steps, 100),
                                                      device, world, rank, detail=False)
@@ -872,7 +932,7 @@ def main():
         if world == 1 and scaling:  # (the round-2 names of the configs[3] / configs[4] per-GPU shards)
             rec["c4_per_gpu"] = scaling["pacs"]
             rec["c5_per_gpu"] = scaling["camelyon_bf16"]
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 rec.update(step_error(cfg, device))
             except Exception as e:  # pragma: no cover

@@ -8,7 +8,7 @@ for r in $(seq $ROUNDS); do
     for lib in "$@"; do
       n=$(basename $lib .so)
       out=gpurun_out/ab/${TAG}_${cfg}_${n}_$r
-      CVHIP_LIB=$lib timeout -k 10 300 python -u bench.py --config $cfg --steps 100 --no-c3 --no-cpu-baseline \
+      CVHIP_LIB=$lib timeout -k 10 300 python -u bench.py --full --config $cfg --steps 100 --no-c3 --no-cpu-baseline \
         --kernel-table $out.txt > $out.log 2>&1 || { echo "$cfg $lib failed"; tail -5 $out.log; exit 1; }
       python -c "import json; d=json.loads(open('$out.log').read().strip().splitlines()[-1]); print('$r', '$cfg', '$n', d['value'], d['ms_per_step'])"
     done

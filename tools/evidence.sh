@@ -11,7 +11,7 @@ O=gpurun_out/ev_$TAG
 for part in $PARTS; do
 case $part in
 bench)
-  timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   tail -c 600 $O/bench.json; echo
   ;;
 trace)

@@ -9,7 +9,7 @@ for cfg in $CFGS; do
   for envs in "$@"; do
     [ "$envs" = "-" ] && envs=""
     out=gpurun_out/kt/${TAG}_${cfg}_$i
-    env $envs timeout -k 10 300 python -u bench.py --config $cfg --steps 100 --no-c3 --no-cpu-baseline \
+    env $envs timeout -k 10 300 python -u bench.py --full --config $cfg --steps 100 --no-c3 --no-cpu-baseline \
       --kernel-table $out.txt > $out.log 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "$cfg [$envs] rc=$rc"; tail -5 $out.log; exit $rc; fi
