@@ -142,12 +142,14 @@ __global__ __launch_bounds__(CMB_NT) void combine_multi_kernel(const CombineArgs
     work[2 * blockIdx.x] = kc;
     work[2 * blockIdx.x + 1] = ks;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
   }
   __syncthreads();
   if (!last) return;
   if (threadIdx.x < 64) {  // (one wave: the partials in workgroup order, a fixed-shape fp64 tree)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const int t = threadIdx.x;
     double a = 0.0, b = 0.0;
     if (t < (int)gridDim.x) {
@@ -183,7 +185,9 @@ __global__ __launch_bounds__(CMB_NT) void combine_multi_kernel(const CombineArgs
 // in wave order, and parks the tile in the workspace.  The last of a tile's S slices to arrive (release / acquire
 // around the tile's ticket) adds the S tiles in slice order and runs the combine of its 256 elements (the arithmetic
 // of combine_sums); the KL partials of the tiles go to the workspace's slots, summed in tile order by the last tile
-// (combine_multi_kernel's protocol).  Every sum has a fixed order.
+// (combine_multi_kernel's protocol).  Every sum has a fixed order.  Both hand-offs publish as cv_gemm_tile.inc's
+// in-launch split-K does: every wave drains its stores (vmcnt(0)) before the barrier, thread 0 releases at agent
+// scope, drains again and takes the ticket; the last to arrive acquires and drains before it reads the others' data.
 constexpr int CDZ_S = 8;  // most F slices (workgroups per 16 x 16 dz tile); default 4 (CV_CDZ_S)
 __global__ __launch_bounds__(256) void combine_dz_kernel(const CombineArgs C, const float* __restrict__ gh,
                                                          const float* __restrict__ W, int F, int pix, int ch, int S,
@@ -240,12 +244,15 @@ __global__ __launch_bounds__(256) void combine_dz_kernel(const CombineArgs C, co
   float g = mine;
   if (S > 1) {
     part[((size_t)tile * S + sl) * 256 + t] = mine;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (every wave's slab stores have landed before the barrier)
     __syncthreads();
     if (t == 0) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       last = __hip_atomic_fetch_add(tticket + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)S - 1;
       if (last) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __hip_atomic_store(tticket + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
@@ -282,11 +289,13 @@ __global__ __launch_bounds__(256) void combine_dz_kernel(const CombineArgs C, co
     work[2 * tile] = kc;
     work[2 * tile + 1] = ks;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     last = __hip_atomic_fetch_add(gticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)ntile - 1;
   }
   __syncthreads();
   if (!last || t >= 64) return;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   double a = 0.0, bsum = 0.0;  // (lane t sums slots t, t + 64, ... in order; then a fixed shuffle tree)
   for (int s2 = t; s2 < ntile; s2 += 64) {
     a += __hip_atomic_load(work + 2 * s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

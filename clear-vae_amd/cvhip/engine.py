@@ -977,16 +977,37 @@ class ClearStep:
         G["graphs"] = graphs
 
     # ----------------------------------------------------------------------------- one step
+    @staticmethod
+    def _raw_copy_ok(G, X, lab) -> bool:
+        """The batch can be copied into the graph's static inputs byte for byte: the buffers' own shapes (a batch of
+        another shape with as many, or fewer, elements is not the same images), dtypes and device, contiguous."""
+        return (X.shape == G["X"].shape and lab.shape == G["lab"].shape and X.dtype == torch.float32
+                and X.is_contiguous() and X.device == G["X"].device and lab.dtype == torch.int64
+                and lab.is_contiguous() and lab.device == G["lab"].device)
+
+    @staticmethod
+    def _check_batch(G, X, lab):
+        """copy_'s own rule (the source broadcasts to the static buffer), for both inputs before either copy is
+        enqueued: a batch the step cannot take raises with nothing of the step on the stream."""
+        for what, src, dst in (("X", X, G["X"]), ("label", lab, G["lab"])):
+            try:
+                ok = torch.broadcast_shapes(tuple(src.shape), tuple(dst.shape)) == tuple(dst.shape)
+            except RuntimeError:
+                ok = False
+            if not ok:
+                raise ValueError(f"step: {what} of shape {tuple(src.shape)} does not fit the step's "
+                                 f"{tuple(dst.shape)} input")
+
     def _load_batch(self, G, X, label):
         """Copy the batch into the graph's static input buffers (one launch when no conversion is needed)."""
         lab = label.reshape(-1)
-        if (X.dtype == torch.float32 and X.is_contiguous() and X.device == G["X"].device and lab.dtype == torch.int64
-                and lab.is_contiguous() and lab.device == G["lab"].device):
+        if self._raw_copy_ok(G, X, lab):
             dst = ptr_array([G["X"].data_ptr(), G["lab"].data_ptr()])
             src = ptr_array([X.data_ptr(), lab.data_ptr()])
             nb = (ctypes.c_size_t * 2)(G["X"].numel() * 4, G["lab"].numel() * 8)
             _lib.call("cv_copy_many", dst, src, nb, 2, _lib.stream_handle())
         else:
+            self._check_batch(G, X, lab)
             G["X"].copy_(X, non_blocking=True)
             G["lab"].copy_(lab, non_blocking=True)
 
@@ -997,6 +1018,9 @@ class ClearStep:
         batch copy into the graph's static inputs folded in (one launch), or the copy by torch and the packing on
         its own when the batch needs a conversion."""
         lab = label.reshape(-1)
+        raw = self._raw_copy_ok(G, X, lab)
+        if not raw:  # (a batch the step cannot take raises here, before the repack below is enqueued)
+            self._check_batch(G, X, lab)
         name, fn, args, _ = G["pack_call"]
         if self.adam_pack:
             if self._packed_sig != self._param_sig():  # (parameters changed outside the engine: repack first)
@@ -1005,10 +1029,8 @@ class ClearStep:
         nbx, nbl = G["X"].numel() * 4, G["lab"].numel() * 8
         # (folded in for small batches only: the pack launch's workgroups hold a 35 KB LDS tile each, so a large copy
         # — VAE64 bs = 256: 12.6 MB — runs slower inside it than as its own launch: CelebA +3 us, MNIST -3 us, measured)
-        if (X.dtype == torch.float32 and X.is_contiguous() and X.device == G["X"].device and lab.dtype == torch.int64
-                and lab.is_contiguous() and lab.device == G["lab"].device and X.numel() * 4 == nbx
-                and lab.numel() * 8 == nbl and nbx % 16 == 0 and nbl % 16 == 0
-                and (X.data_ptr() | lab.data_ptr()) % 16 == 0 and nbx + nbl <= self.PACK_COPY_MAX):
+        if (raw and nbx % 16 == 0 and nbl % 16 == 0 and (X.data_ptr() | lab.data_ptr()) % 16 == 0
+                and nbx + nbl <= self.PACK_COPY_MAX):
             dst = ptr_array([G["X"].data_ptr(), G["lab"].data_ptr()])
             src = ptr_array([X.data_ptr(), lab.data_ptr()])
             nb = (ctypes.c_size_t * 2)(nbx, nbl)
@@ -1033,7 +1055,9 @@ class ClearStep:
         self._packed_sig = None
 
     def step(self, X, label, before_update=None):
-        """One training step on the batch (X, label).  before_update: an optional callable run (on the host, in
+        """One training step on the batch (X [n][C][H][W], label [n]; a batch of another shape that does not
+        broadcast to the step's static inputs raises before anything is enqueued).  before_update: an optional
+        callable run (on the host, in
         stream order: the step's kernels before it are enqueued, none after) once the gradients are complete —
         all-reduced under DP — and before the Adam launch; such a step runs eagerly, not from the graph (used by
         the tests to read the step's activations with the pre-update parameters)."""

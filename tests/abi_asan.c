@@ -107,6 +107,43 @@ int main(void) {
   EXPECT_ERR(cv_group_forward(5, dp, dp, 32, lp, 64, 8, dp, NULL, NULL, NULL, 0, NULL, 0, 0, NULL, NULL, st),
              "group_forward: unknown mode");
   EXPECT(cv_tc_workspace_bytes(16) > 0, "tc_workspace_bytes");
+  /* the latent combine with the decoder-input gradient (MNIST: K = 16, F = 2048 = 16 pixels x 128 channels) */
+  EXPECT(cv_latent_combine_dz_workspace_bytes(64, 8) > cv_latent_combine_workspace_bytes(),
+         "latent_combine_dz_workspace_bytes");
+  EXPECT(cv_latent_combine_dz_workspace_bytes(0, 8) == 0, "latent_combine_dz_workspace_bytes (n = 0)");
+  double* wk = (double*)dp;
+  cv_linear dl = {64, 16, 2048, 1, 0, 16, 128, CV_MMA_FP32};
+  EXPECT_ERR(cv_latent_combine_dz(dp, dp, dp, dp, &dl, 1.f, 0.f, 1.f, lp, NULL, dp, dp, NULL, 1, NULL, st),
+             "latent_combine_dz: no workspace");
+  EXPECT_ERR(cv_latent_combine_dz(dp, dp, dp, dp, NULL, 1.f, 0.f, 1.f, lp, NULL, dp, dp, NULL, 1, wk, st),
+             "latent_combine_dz: null geometry");
+  EXPECT_ERR(cv_latent_combine_dz(dp, dp, NULL, dp, &dl, 1.f, 0.f, 1.f, lp, NULL, dp, dp, NULL, 1, wk, st),
+             "latent_combine_dz: null d(h)");
+  dl.out_features = 2080; /* F % 64 != 0 */
+  EXPECT_ERR(cv_latent_combine_dz(dp, dp, dp, dp, &dl, 1.f, 0.f, 1.f, lp, NULL, dp, dp, NULL, 1, wk, st),
+             "latent_combine_dz: F % 64 != 0");
+  dl.out_features = 2048;
+  dl.in_features = 15; /* K = 2d */
+  EXPECT_ERR(cv_latent_combine_dz(dp, dp, dp, dp, &dl, 1.f, 0.f, 1.f, lp, NULL, dp, dp, NULL, 1, wk, st),
+             "latent_combine_dz: odd K");
+  dl.in_features = 16;
+  dl.out_ch = 64; /* 16 x 64 != 2048 */
+  EXPECT_ERR(cv_latent_combine_dz(dp, dp, dp, dp, &dl, 1.f, 0.f, 1.f, lp, NULL, dp, dp, NULL, 1, wk, st),
+             "latent_combine_dz: out_pix*out_ch != out_features");
+  dl.out_features = 192; /* 32 pixels x 6 channels: a float4 of d(h) would span two pixels */
+  dl.out_pix = 32;
+  dl.out_ch = 6;
+  EXPECT_ERR(cv_latent_combine_dz(dp, dp, dp, dp, &dl, 1.f, 0.f, 1.f, lp, NULL, dp, dp, NULL, 1, wk, st),
+             "latent_combine_dz: out_ch % 4 != 0");
+  dl.out_features = 2048;
+  dl.out_pix = 16;
+  dl.out_ch = 128;
+  EXPECT_ERR(cv_latent_combine_dz(dp, dp, dp + 1, dp, &dl, 1.f, 0.f, 1.f, lp, NULL, dp, dp, NULL, 1, wk, st),
+             "latent_combine_dz: misaligned d(h)");
+  dl.n = 8208; /* 513 row tiles x 2 column tiles > 1024 slots */
+  dl.in_features = 32;
+  EXPECT_ERR(cv_latent_combine_dz(dp, dp, dp, dp, &dl, 1.f, 0.f, 1.f, lp, NULL, dp, dp, NULL, 1, wk, st),
+             "latent_combine_dz: more than 1024 dz tiles");
 
   /* ---- input pipeline: the host-built Pillow plan, exactly sized and undersized */
   const int sizes[][4] = {{96, 96, 64, 64}, {224, 224, 64, 64}, {227, 227, 64, 64}, {28, 28, 28, 28},

@@ -26,7 +26,8 @@ def test_header_declares_the_hot_path():
                  "cv_output_loss", "cv_reparam_forward", "cv_latent_combine", "cv_ntxent", "cv_mi_forward",
                  "cv_mi_backward", "cv_mi_learning_step", "cv_adam_step", "cv_last_error", "cv_pack_conv_weights",
                  "cv_latent_step", "cv_step_reduce", "cv_conv_backward_weight_deferred",
-                 "cv_linear_backward_weight_deferred", "cv_tc_forward", "cv_tc_learning_step"):
+                 "cv_linear_backward_weight_deferred", "cv_tc_forward", "cv_tc_learning_step",
+                 "cv_latent_combine_acc", "cv_latent_combine_dz", "cv_latent_combine_dz_workspace_bytes"):
         assert need in fns, need
 
 
