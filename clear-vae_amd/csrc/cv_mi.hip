@@ -17,6 +17,11 @@
 // L1OutUB follows the reference's broadcasting exactly (mi_estimator.py:181-191):
 //   negative[b,c] = all_probs[b,c] + log(N-1 + e^-20) - log(N-1), result = mean_{b,c}(pos_c - neg_{b,c})
 // which reduces to mean_c pos_c - mean_{b,c} all_probs[b,c] - delta, computed in O(N d).
+// CLUB (mi_estimator.py:43-55) is the same structure without the sampling: its negative term
+//   mean_j (y_jd - mu_id)^2 = (Sy2_d - 2 mu_id Sy_d + N mu_id^2) / N
+// comes from the column moments the perm kernel leaves for L1OutUB, so it is O(N d) as well; dCLUB/dy needs the
+// E_d = sum_i 1/v_id, M_d = sum_i mu_id/v_id the rows kernel folds.  VarUB (mi_estimator.py:222-224) is the mean
+// over the N*dy elements of (mu^2 + e^lv - 1 - lv)/2 and does not depend on y.
 #include "cv_common.hpp"
 
 namespace cv {
@@ -317,8 +322,8 @@ __global__ __launch_bounds__(1024) void mi_perm_kernel(const MiArgs A) {
         W.invperm[p] = i;
       }
     }
-  } else {
-    // column sums of y (fp64): lane = column, 16 row groups folded in group order
+  } else if (A.kind != CV_MI_VARUB) {
+    // column sums of y (fp64; L1OutUB and CLUB): lane = column, 16 row groups folded in group order
     const int k = t & 63, g = t >> 6;
     double s = 0.0, q = 0.0;
     if (k < A.P.dy)
@@ -352,8 +357,8 @@ __global__ __launch_bounds__(256) void mi_rows_kernel(const MiArgs A) {
   const int n = A.n, t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int dx = A.P.dx, h = A.P.h, dy = A.P.dy;
   MiWork W = mi_work(A.work, n);
-  double acc0 = 0.0, acc1 = 0.0;  // CLUB: sum(pos-neg); L1Out: sum pos, sum A_b
-  double eacc = 0.0, macc = 0.0;  // L1Out: per-lane E_k, M_k partials
+  double acc0 = 0.0, acc1 = 0.0;  // CLUB-S: sum(pos-neg); L1Out: sum pos, sum A_b; CLUB, VarUB: acc1 = sum of terms
+  double eacc = 0.0, macc = 0.0;  // L1Out, CLUB: per-lane E_k, M_k partials
   for (int r = blockIdx.x * 4 + w; r < n; r += gridDim.x * 4) {
     RowF f;
     mlp_fwd_row<DM>(L, dx, h, dy, A.x + (size_t)r * A.ldx, lane, f);
@@ -367,13 +372,24 @@ __global__ __launch_bounds__(256) void mi_rows_kernel(const MiArgs A) {
         const float pos = -((f.mu - yv) * (f.mu - yv)) / el;
         const float neg = -((f.mu - yp) * (f.mu - yp)) / el;
         term = pos - neg;
-      } else {
+      } else if (A.kind == CV_MI_L1OUT) {
         const float df = f.mu - yv;
         term = -(df * df) / 2.0f / el - f.lv / 2.0f;
         const double Sy = W.sums[lane], Sy2 = W.sums[64 + lane], m = f.mu;
         dterm = -(Sy2 - 2.0 * m * Sy + (double)n * m * m) / (2.0 * (double)el) - (double)n * (double)f.lv / 2.0;
         eacc += 1.0 / (double)el;
         macc += m / (double)el;
+      } else if (A.kind == CV_MI_CLUB) {
+        // pos - neg of one element, the subtraction in fp64 (two sums of order 10 whose difference is of order 0.1)
+        const double Sy = W.sums[lane], Sy2 = W.sums[64 + lane], m = f.mu;
+        const double df = m - (double)yv;
+        const double sq = Sy2 - 2.0 * m * Sy + (double)n * m * m;
+        dterm = (sq / (double)n - df * df) / (2.0 * (double)el);
+        eacc += 1.0 / (double)el;
+        macc += m / (double)el;
+      } else {  // VarUB
+        const double m = f.mu;
+        dterm = 0.5 * (m * m + (double)el - 1.0 - (double)f.lv);
       }
     }
     acc0 += wave_sum((double)term);
@@ -433,10 +449,14 @@ __global__ __launch_bounds__(256) void mi_rows_kernel(const MiArgs A) {
     double mi;
     if (A.kind == CV_MI_CLUBSAMPLE) {
       mi = a0 / (double)n / 2.0;
-    } else {
+    } else if (A.kind == CV_MI_L1OUT) {
       const double nn = (double)n;
       const double delta = log((nn - 1.0) + exp(-20.0)) - log(nn - 1.0);
       mi = a0 / nn - a1 / (nn * nn) - delta;
+    } else if (A.kind == CV_MI_CLUB) {
+      mi = a1 / (double)n;
+    } else {  // VarUB: the mean runs over the elements, not over the rows
+      mi = a1 / ((double)n * (double)dy);
     }
     if (A.mi_out) A.mi_out[0] = (float)mi;
   }
@@ -476,6 +496,25 @@ __global__ __launch_bounds__(256) void mi_grad_kernel(const MiArgs A) {
         const float yv = A.y[(size_t)r * A.ldy + lane];
         dyv += c * (-2.f) * (fq.mu - yv) / expf(fq.lv);
       }
+    } else if (A.kind == CV_MI_CLUB) {
+      if (lane < dy) {
+        const double nn = (double)n;
+        const float yv = A.y[(size_t)r * A.ldy + lane];
+        const double el = (double)expf(f.lv), m = f.mu, df = m - (double)yv;
+        const double Sy = W.sums[lane], Sy2 = W.sums[64 + lane];
+        const double E = W.sums[128 + lane], M = W.sums[192 + lane];
+        dmu = g * (float)(((double)yv - Sy / nn) / (nn * el));
+        // the two halves of d/dlogvar subtracted in fp64, as the forward's terms are
+        const double sq = Sy2 - 2.0 * m * Sy + nn * m * m;
+        dlv = g * (float)((df * df - sq / nn) / (2.0 * el * nn));
+        dyv = g * (float)(df / (nn * el) + ((double)yv * E - M) / (nn * nn));
+      }
+    } else if (A.kind == CV_MI_VARUB) {
+      if (lane < dy) {
+        const float c = g / ((float)n * (float)dy);
+        dmu = c * f.mu;
+        dlv = c * 0.5f * expm1f(f.lv);
+      }
     } else {
       const float nn = (float)n;
       if (lane < dy) {
@@ -509,7 +548,8 @@ __global__ __launch_bounds__(256) void mi_grad_kernel(const MiArgs A) {
         float* p = A.dx + (size_t)r * A.gld + lane;
         *p = A.accumulate ? *p + dxv : dxv;
       }
-      if (A.dy && lane < dy) {
+      // (VarUB does not depend on y: zeros when written, dy left as it is when accumulated)
+      if (A.dy && lane < dy && !(A.kind == CV_MI_VARUB && A.accumulate)) {
         float* p = A.dy + (size_t)r * A.gld + lane;
         *p = A.accumulate ? *p + dyv : dyv;
       }
@@ -854,6 +894,10 @@ static int mlp_dm(const cv_mlp* P) {
     else hipLaunchKernelGGL(KERNEL<64>, grid, block, 0, st, arg);                 \
   } while (0)
 
+static bool known_kind(int kind) {
+  return kind == CV_MI_CLUBSAMPLE || kind == CV_MI_L1OUT || kind == CV_MI_CLUB || kind == CV_MI_VARUB;
+}
+
 static int mi_row_blocks(int n) {
   const int b = cdiv(n, 4);
   return b < MI_NB ? b : MI_NB;
@@ -864,7 +908,7 @@ extern "C" int cv_mi_forward(int kind, const cv_mlp* mlp, const float* x, int ld
                              cv_stream_t stream) {
   clear_error();
   if (check_mlp(mlp)) return 1;
-  CV_REQUIRE(kind == CV_MI_CLUBSAMPLE || kind == CV_MI_L1OUT, "mi: unknown estimator %d", kind);
+  CV_REQUIRE(known_kind(kind), "mi: unknown estimator %d", kind);
   CV_REQUIRE(x && y && work && n > 1 && n <= MI_MAXBIG, "mi_forward: bad args (2 <= n <= %d)", MI_MAXBIG);
   CV_REQUIRE(kind != CV_MI_CLUBSAMPLE || perm || offset, "mi_forward: CLUBSample needs perm or an RNG offset");
   MiArgs a;
@@ -892,6 +936,7 @@ extern "C" int cv_mi_backward(int kind, const cv_mlp* mlp, const float* x, int l
                               float* dheads, int d, cv_stream_t stream) {
   clear_error();
   if (check_mlp(mlp)) return 1;
+  CV_REQUIRE(known_kind(kind), "mi: unknown estimator %d", kind);
   CV_REQUIRE(x && y && work && n > 1 && n <= MI_MAXBIG, "mi_backward: bad args");
   CV_REQUIRE(!dheads || (heads && z && d == mlp->dx && d == mlp->dy), "mi_backward: chain mode needs heads, z, d");
   MiArgs a;

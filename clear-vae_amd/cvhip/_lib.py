@@ -31,7 +31,7 @@ def stat_repl(C: int) -> int:
 XF_NONE, XF_BNRELU, XF_BNBWD = 0, 1, 2
 STAT_NONE, STAT_FWD, STAT_BWD = 0, 1, 2
 SIM = {"cosine": 0, "l2": 1, "modified_l2": 2, "jeffrey": 3, "mahalanobis": 4}
-MI_NONE, MI_CLUBSAMPLE, MI_L1OUT = 0, 1, 2
+MI_NONE, MI_CLUBSAMPLE, MI_L1OUT, MI_CLUB, MI_VARUB = 0, 1, 2, 3, 4  # CV_MI_*
 MMA_FP32, MMA_BF16 = 0, 1  # CV_MMA_*
 GROUP = {"MLVAE": 0, "GVAE": 1}  # CV_GROUP_*
 PRECISION = {"fp32": MMA_FP32, "bf16": MMA_BF16}

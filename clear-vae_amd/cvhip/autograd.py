@@ -374,7 +374,8 @@ def est_params(est):
 
 
 class MIUpperBoundFn(torch.autograd.Function):
-    """CLUBSample.forward / L1OutUB.forward (mi_estimator.py:133-143, 170-191)."""
+    """CLUBSample.forward / L1OutUB.forward (mi_estimator.py:133-143, 170-191) and CLUB.forward / VarUB.forward
+    (mi_estimator.py:43-55, 222-224); only CLUBSample takes a permutation."""
 
     @staticmethod
     def forward(ctx, x, y, est, kind, *params):

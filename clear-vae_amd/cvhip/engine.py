@@ -42,12 +42,15 @@ import torch.distributed as dist
 
 from . import _lib, rng
 from . import dist as cvdist
-from ._lib import (GROUP, MI_CLUBSAMPLE, MI_L1OUT, SIM, cv_latent_chain, cv_mlp, cv_mlp_grad, cv_ntxent_branch,
-                   cv_tc_disc, cv_tc_grad)
+from ._lib import (GROUP, MI_CLUB, MI_CLUBSAMPLE, MI_L1OUT, MI_VARUB, SIM, cv_latent_chain, cv_mlp, cv_mlp_grad,
+                   cv_ntxent_branch, cv_tc_disc, cv_tc_grad)
 from .autograd import est_params, mlp_struct
 from ._lib import cv_conv_pack
 from .plan import (DeferGroup, ParamArena, Program, Workspace, ensure_arena, pack_program, ptr_array,
                    struct_array)
+
+# the estimator classes of src.models.mi_estimator the fused CLEAR-MIM step carries, and their CV_MI_* kind
+MI_KINDS = {"CLUBSample": MI_CLUBSAMPLE, "L1OutUB": MI_L1OUT, "CLUB": MI_CLUB, "VarUB": MI_VARUB}
 
 
 # CVHIP_FUSED_ADAM=1: single-process steps run the optimizer inside the end-of-backward reduction
@@ -273,10 +276,10 @@ class ClearStep:
         elif trainer.sim_fn not in SIM:
             raise ValueError("unimplemented similarity measure.")
         if mode == "mim":
-            from src.models.mi_estimator import CLUBSample, L1OutUB
+            from src.models.mi_estimator import CLUB, CLUBSample, L1OutUB, VarUB
 
             est = trainer.mi_estimator
-            if type(est) not in (CLUBSample, L1OutUB):
+            if type(est) not in (CLUBSample, L1OutUB, CLUB, VarUB):
                 return None
             if not _AdamState.supported(trainer.mi_estimator_optimizer, est_params(est)):
                 return None
@@ -329,7 +332,7 @@ class ClearStep:
             self.est = trainer.mi_estimator
             self.est_arena = ParamArena(est_params(self.est), self.device)
             self.est_adam = _AdamState(trainer.mi_estimator_optimizer, self.est_arena)
-            self.kind = MI_CLUBSAMPLE if type(self.est).__name__ == "CLUBSample" else MI_L1OUT
+            self.kind = MI_KINDS[type(self.est).__name__]
             self.learn = torch.zeros(5, dtype=torch.float32, device=self.device)
         if mode == "tc":  # the factor discriminator plays the estimator's part: its own arena + Adam
             self.est = trainer.factor_cls

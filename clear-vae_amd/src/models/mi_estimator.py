@@ -1,10 +1,14 @@
 """MI upper-bound estimators with the reference's modules and method names
-(code/src/models/mi_estimator.py).  CLUBSample and L1OutUB — the two estimators the CLEAR-MIM
-trainer instantiates — run on libclearvae_hip.so: forward / learning_loss /
-their gradients are HIP kernels (cvhip.autograd.MIUpperBoundFn / LearningLossFn).
+(code/src/models/mi_estimator.py).  The four estimators over the q(y|x) network pair (p_mu, p_logvar) —
+CLUBSample and L1OutUB, which the CLEAR-MIM scripts instantiate, and CLUB and VarUB,
+which `get_clearmimvae_trainer(mi_estimator=...)` resolves as well — run on libclearvae_hip.so: forward /
+learning_loss / their gradients are HIP kernels (cvhip.autograd.MIUpperBoundFn / LearningLossFn), and
+ClearStep fuses all four.  CLUB and VarUB keep their plain-PyTorch forward on CPU tensors (they never
+raised there); CLUBSample and L1OutUB require the GPU.
 
-CLUB, CLUBMean, VarUB and InfoNCE are never instantiated by a CLEAR trainer, factory, script or
-demo; they are kept importable as plain PyTorch tensor code.
+CLUBMean (a different network: no p_logvar) and InfoNCE (a lower bound with a critic network) are never
+instantiated by a CLEAR trainer, script or demo; they are kept importable as plain
+PyTorch tensor code.
 """
 
 from __future__ import annotations
@@ -14,7 +18,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from cvhip import autograd as _ag
-from cvhip._lib import MI_CLUBSAMPLE, MI_L1OUT
+from cvhip._lib import MI_CLUB, MI_CLUBSAMPLE, MI_L1OUT, MI_VARUB
 
 
 def _q_nets(x_dim, y_dim, hidden_size):
@@ -60,15 +64,31 @@ class L1OutUB(_QEstimator):
         return _ag.MIUpperBoundFn.apply(x_samples, y_samples, self, MI_L1OUT, *_ag.est_params(self))
 
 
-# ----------------------------------------------------------------------------- not on the hot path
-
-
 class CLUB(_QEstimator):
+    """The non-sampled CLUB bound (mi_estimator.py:43-55).  On the GPU the [N, N, d] negative term is evaluated
+    through the column moments of y in O(N d); on CPU tensors the reference's broadcast formula."""
+
     def forward(self, x_samples, y_samples):
+        if x_samples.device.type == "cuda":
+            return _ag.MIUpperBoundFn.apply(x_samples, y_samples, self, MI_CLUB, *_ag.est_params(self))
         mu, logvar = self.get_mu_logvar(x_samples)
         positive = -((mu - y_samples) ** 2) / 2.0 / logvar.exp()
         negative = -((y_samples.unsqueeze(0) - mu.unsqueeze(1)) ** 2).mean(dim=1) / 2.0 / logvar.exp()
         return (positive.sum(dim=-1) - negative.sum(dim=-1)).mean()
+
+
+class VarUB(_QEstimator):
+    """Variational upper bound (mi_estimator.py:222-224): the mean over all N * y_dim elements; independent of
+    y_samples.  HIP kernels on the GPU, the reference's formula on CPU tensors."""
+
+    def forward(self, x_samples, y_samples):
+        if x_samples.device.type == "cuda":
+            return _ag.MIUpperBoundFn.apply(x_samples, y_samples, self, MI_VARUB, *_ag.est_params(self))
+        mu, logvar = self.get_mu_logvar(x_samples)
+        return 1.0 / 2.0 * (mu**2 + logvar.exp() - 1.0 - logvar).mean()
+
+
+# ----------------------------------------------------------------------------- not on the hot path
 
 
 class CLUBMean(nn.Module):
@@ -94,12 +114,6 @@ class CLUBMean(nn.Module):
 
     def learning_loss(self, x_samples, y_samples):
         return -self.loglikeli(x_samples, y_samples)
-
-
-class VarUB(_QEstimator):
-    def forward(self, x_samples, y_samples):
-        mu, logvar = self.get_mu_logvar(x_samples)
-        return 1.0 / 2.0 * (mu**2 + logvar.exp() - 1.0 - logvar).mean()
 
 
 def logsumexp(x: Tensor, dim: int) -> Tensor:

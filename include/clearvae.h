@@ -471,8 +471,8 @@ int cv_latent_step(const float* heads, const float* z, const float* dz, int n, i
                    float* dheads, float* losses, const cv_ntxent_branch* br, int nbr,
                    const int64_t* label, int sim, float temperature, cv_stream_t stream);
 
-/* ---- MI upper bounds (mi_estimator.py:108-198) ---- */
-enum { CV_MI_NONE = 0, CV_MI_CLUBSAMPLE = 1, CV_MI_L1OUT = 2 };
+/* ---- MI upper bounds (mi_estimator.py:108-198; CLUB: mi_estimator.py:43-55, VarUB: mi_estimator.py:222-224) ---- */
+enum { CV_MI_NONE = 0, CV_MI_CLUBSAMPLE = 1, CV_MI_L1OUT = 2, CV_MI_CLUB = 3, CV_MI_VARUB = 4 };
 
 /* q(y|x) MLPs (mi_estimator.py:111-122): p_mu = L(dx,h)-ReLU-L(h,dy);
  * p_logvar = L(dx,h)-ReLU-L(h,dy)-Tanh; Linear weights [out][in]; h = hidden_size // 2. */
@@ -488,8 +488,10 @@ typedef struct cv_mlp_grad {
 size_t cv_mi_workspace_bytes(int n);
 /* CLUBSample.forward (mi_estimator.py:133-143; perm injected, or generated on device from
  * (seed, offset)) and L1OutUB.forward (mi_estimator.py:170-191, with the reference's [N,N,N]
- * broadcasting reduced to its O(N d) closed form).  Writes mi_out[0]; leaves perm / column sums
- * in `work` for cv_mi_backward. */
+ * broadcasting reduced to its O(N d) closed form).  CV_MI_CLUB (mi_estimator.py:43-55): the [N,N,d] negative
+ * term through the fp64 column moments of y, O(N d); CV_MI_VARUB (mi_estimator.py:222-224): the mean over the N*dy
+ * elements, independent of y.  Neither of the two needs perm or offset (an offset given advances as for L1OutUB).
+ * Writes mi_out[0]; leaves perm / column sums in `work` for cv_mi_backward. */
 int cv_mi_forward(int kind, const cv_mlp* mlp, const float* x, int ldx, const float* y, int ldy,
                   int n, const int64_t* perm, uint64_t seed, uint64_t* offset, void* work,
                   float* mi_out, cv_stream_t stream);
