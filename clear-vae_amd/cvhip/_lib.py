@@ -370,6 +370,11 @@ _SIGS = {
         [_P(cv_mlp), c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, _P(cv_mlp_grad), c_void_p,
          c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     ),
+    "cv_knn_mi_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "cv_knn_mi": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     "cv_adam_step": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],

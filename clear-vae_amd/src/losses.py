@@ -6,10 +6,13 @@ Hot path — HIP kernels through cvhip.autograd:
 The pairwise_* / snn_loss / logsumexp helpers keep the reference's tensor-level semantics for
 callers that use them directly (they are building blocks, not the trained path); the supcon / lam
 losses and the sklearn metrics are outside the hot path and stay as in the
-reference (sklearn on CPU).
+reference (sklearn on CPU); gMIG also has a device backend (cv_knn_mi through cvhip.metrics), chosen
+per call or with the environment variable CVHIP_GMIG.
 """
 
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn.functional as F
@@ -23,8 +26,22 @@ from cvhip._lib import SIM
 # ----------------------------------------------------------------------------- metrics (CPU)
 
 
-def mutual_info_gap(label, latent_c, latent_s):
-    """gMIG (losses.py:10-16): sklearn kNN MI on the CPU, as in the reference."""
+GMIG_BACKENDS = ("sklearn", "device")
+
+
+def mutual_info_gap(label, latent_c, latent_s, backend=None):
+    """gMIG (losses.py:10-16).  backend "sklearn" (the default) is the reference's computation: sklearn kNN MI on
+    host copies of the latents.  "device" is the same estimator as a HIP kernel (cvhip.metrics.gmig): the latents
+    stay on the device, ties are broken by index instead of sklearn's random noise, the value is deterministic.
+    backend=None takes the environment variable CVHIP_GMIG when it is set, else "sklearn"."""
+    if backend is None:
+        backend = os.environ.get("CVHIP_GMIG") or "sklearn"
+    if backend not in GMIG_BACKENDS:
+        raise ValueError(f"mutual_info_gap: unknown backend {backend!r} (one of {', '.join(GMIG_BACKENDS)})")
+    if backend == "device":
+        from cvhip import metrics as _metrics
+
+        return _metrics.gmig(label, latent_c, latent_s)
     label, latent_c, latent_s = label.cpu(), latent_c.cpu(), latent_s.cpu()
     p = torch.bincount(label) / len(label)
     H = float(-(p * torch.log(p)).sum())

@@ -99,7 +99,8 @@ def _batch(batch, device, transform):
 
 class _ClearEval:
     """evaluate() shared by the CLEAR trainers (trainer.py:495-570, 899-965): eval-mode forward on the
-    HIP path under no_grad, the same losses, gMIG on the CPU."""
+    HIP path under no_grad, the same losses, gMIG by mutual_info_gap (sklearn on the CPU as in the reference, or
+    the device kernel with CVHIP_GMIG=device)."""
 
     def _evaluate(self, dataloader, verbose, epoch_id, last_name, last_fn):
         vae = self.model

@@ -584,6 +584,20 @@ int cv_load_batch_u8(const uint8_t* images, int in_h, int in_w, int c, const int
                      const int64_t* labels, int64_t* labels_out, const int64_t* styles, int64_t* styles_out,
                      cv_stream_t stream);
 
+/* ---- evaluation metric: kNN mutual information, the estimator behind gMIG (losses.py:10-16, where
+ * mutual_info_gap calls sklearn's mutual_info_classif twice: Ross 2014, continuous feature against a discrete
+ * label, one KD-tree per latent dimension on the host) ----
+ * x: [n][d] fp32 with row stride ldx >= d; cls: the compact class id of each point, or -1 for a point that takes
+ * part in nothing (its label occurs once).  Per feature f and kept point i, with D_ij = |(double)x_jf - (double)x_if|
+ * and neighbours ordered by the key (D_ij, j): j* = the min(k, cnt_i - 1)-th smallest key among kept j != i of i's
+ * class, m_i = 1 + #{kept j != i : (D_ij, j) < (D_ij*, j*)} (sklearn's radius count, ties broken by index where
+ * sklearn adds noise).  m_out [d][n] (or NULL) receives m_i (0 where not kept), psi_sum_out [d] = sum over kept i
+ * of psi[m_i] with psi a device table psi[1..n] (n + 1 entries; entry 0 unused), added in a fixed order: the result
+ * is bit-reproducible.  1 <= k <= 8, n >= 2; work: cv_knn_mi_workspace_bytes(n, d) bytes, need not be zeroed. */
+size_t cv_knn_mi_workspace_bytes(int n, int d);
+int cv_knn_mi(const float* x, int ldx, int n, int d, const int32_t* cls, int k, const double* psi, int32_t* m_out,
+              double* psi_sum_out, void* work, cv_stream_t stream);
+
 /* ---- Adam (torch.optim.Adam foreach semantics) over a flat fp32 arena ----
  * hyper: device float[8] = lr, beta1, beta2, eps, weight_decay; step: device int64[2] =
  * (steps taken, arrival counter = 0).  grad_scale (device float or NULL) multiplies the gradient
