@@ -4,8 +4,8 @@
 // Why: the contrastive terms (trainer.py:474-479 through losses.py:98-137) depend only on the heads,
 // yet their two launches (row log-sum-exps, then the losses and gradients) sat on the step's critical path between
 // the decoder backward and the heads backward: 31 us of the MNIST step in two small grids (256 workgroups each).
-// A second stream in the replayed graph costs more than that in fork / join edges (measured, cvhip/engine.py
-// LATENT_SIDE), so the phases ride in grids that already run: the rows phase in the first decoder ConvTranspose2d's
+// A second stream in the replayed graph costs more than that in fork / join edges (measured, DESIGN.md §4: that
+// schedule was removed), so the phases ride in grids that already run: the rows phase in the first decoder ConvTranspose2d's
 // forward, the gradient phase in the second's (the gradients accumulate into a d(heads) the step's first launch
 // zeroed; the KL / decoder-chain seed, cv_latent_combine_acc, adds onto them later).  The roles alternate over the
 // first 2 x min(direct, aux) workgroups so every CU gets some of each; the grid's LDS and registers are the larger

@@ -36,6 +36,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from dataclasses import dataclass
 
 import torch
 import torch.distributed as dist
@@ -53,11 +54,6 @@ from .plan import (DeferGroup, ParamArena, Program, Workspace, ensure_arena, pac
 MI_KINDS = {"CLUBSample": MI_CLUBSAMPLE, "L1OutUB": MI_L1OUT, "CLUB": MI_CLUB, "VarUB": MI_VARUB}
 
 
-# CVHIP_FUSED_ADAM=1: single-process steps run the optimizer inside the end-of-backward reduction
-# (cv_step_reduce_adam: one launch less, but the reduction's gradient order makes the Adam read-modify-writes
-# strided; MNIST 777k vs 791k img/s, CelebA 99.7k vs 102.3k), so the separate cv_adam_step stays the default
-FUSED_ADAM = os.environ.get("CVHIP_FUSED_ADAM", "0") == "1"  # measured slower (strided Adam RMW): off
-
 # CVHIP_GRAPH_COLLECTIVES=1 (opt-in): a data-parallel step is captured as ONE graph with its RCCL all-reduces inside
 # (issued on the capturing stream: the process group's collective stream joins the capture behind an event edge, the
 # collective's branch runs beside the next backward segment and the Adam segment waits on it), so a step is one
@@ -68,18 +64,7 @@ FUSED_ADAM = os.environ.get("CVHIP_FUSED_ADAM", "0") == "1"  # measured slower (
 # its CUDA-event cache off (cvhip.dist.captured_collectives_group), so no caller setup is needed.
 GRAPH_COLLECTIVES = os.environ.get("CVHIP_GRAPH_COLLECTIVES", "0") == "1"
 
-# CVHIP_LATENT_SIDE=1 (A/B knob, off: measured slower): the NT-Xent terms depend only on the heads, so their two launches (row
-# log-sum-exps, then the gradients, accumulated into a d(heads) the step's first launch zeroed) fork onto a side
-# stream right after the heads launch and run beside the decoder forward / backward; the step joins them before the
-# KL / decoder-chain seed (cv_latent_combine_acc), which now adds onto them.  The same two adds per element, in the
-# other order: d(heads) is bit-identical.  Single-graph steps only (a data-parallel step captured per segment would
-# leave the fork unjoined in its first graph).  Measured (round 5, same box, 2 rounds): MNIST 0.5155 -> 0.5241 ms,
-# C3 4.236 -> 4.276 ms — the graph's fork / join edges cost more than the 31 us of NT-Xent they take off the
-# critical path, as for the side-stream weight gradients; so the two launches stay on the critical
-# path (cv_latent_step).
-LATENT_SIDE = os.environ.get("CVHIP_LATENT_SIDE", "0") == "1"
-
-# CVHIP_LATENT_AUX (default 1): the NT-Xent phases queued into the decoder forward instead (cv_ntxent_aux): the row
+# CVHIP_LATENT_AUX (default 1): the NT-Xent phases queued into the decoder forward (cv_ntxent_aux): the row
 # log-sum-exps ride in the first decoder ConvTranspose2d's grid, the losses and gradients (accumulated into the
 # zeroed d(heads)) in the second's, as extra workgroups of the same launch where the library serves the pair
 # (cv_aux.hip), else as their own launches at those points; the KL / decoder-chain seed adds onto them after the
@@ -115,7 +100,7 @@ LATENT_CHAIN = os.environ.get("CVHIP_LATENT_CHAIN", "0") == "1"
 LATENT_AUX_DL = int(os.environ.get("CVHIP_LATENT_AUX_DL", "1"))
 
 # CVHIP_ADAM_PACK (default auto: on for arenas of >= 2^20 parameters, i.e. VAE64; 1 / 0 force; single GPU and data
-# parallel, not with CVHIP_FUSED_ADAM): the VAE's Adam step packs the
+# parallel): the VAE's Adam step packs the
 # conv weights it has just updated in the same launch (cv_adam_pack_step), so the packed copies are current when the
 # next forward starts: a replayed step's first launch only zeroes (and copies the batch), and CLEAR-MIM's / CLEAR-TC's
 # estimator forwards after the update need no packing launch.  Parameters changed outside the engine between steps
@@ -128,7 +113,7 @@ LATENT_AUX_DL = int(os.environ.get("CVHIP_LATENT_AUX_DL", "1"))
 ADAM_PACK = os.environ.get("CVHIP_ADAM_PACK", "auto")
 ADAM_PACK_MIN = 1 << 20
 
-# CVHIP_DET_DZ (default 1; the LATENT_AUX / LATENT_SIDE schedules): the decoder-input gradient dz = d(h) W is computed
+# CVHIP_DET_DZ (default 1; the LATENT_AUX schedules): the decoder-input gradient dz = d(h) W is computed
 # by the latent combine launch (cv_latent_combine_dz, fixed-order sums) instead of as fp32-atomic partials in the
 # decoder-input backward — the fused step's only order-dependent sum, so with it replays from the same state are
 # bit-identical (tests/test_gpu_determinism.py); 0: the atomic partials (A/B)
@@ -136,17 +121,12 @@ DET_DZ = os.environ.get("CVHIP_DET_DZ", "1") == "1"
 
 # CVHIP_MIM_BRANCHES (default 2; 0: the sequential form): CLEAR-MIM's five estimator-update decoder forwards
 # (trainer.py:873-888) on this many side lanes of the single-GPU step graph, beside the five estimator learning steps
-# on the step's stream (ClearStep._programs, make_learn_branched).  Measured (round 6, VAE64 n = 256, the five
+# on the step's stream (ClearStep._mim_learn_programs).  Measured (round 6, VAE64 n = 256, the five
 # decoder forwards alone in a graph, scratch experiment): back to back 1.50 ms; on 5 / 3 / 2 lanes 1.23 / 1.20 /
 # 1.25 ms; one decoder pass over 5 x 256 images (the bound of a segmented-statistics kernel) 1.27 ms.  In the step,
 # with the side-stream weight gradients of the VAE step (WGRAD_LANE): 1 / 2 / 3 lanes 3.730 / 3.511 / 3.480 ms on one
 # box (two rounds), 2 / 3 lanes 3.497 / 3.529 ms on another: 2 and 3 within the boxes' spread, 2 kept.
 MIM_BRANCHES = int(os.environ.get("CVHIP_MIM_BRANCHES", "2"))
-
-# CVHIP_PACK_COPY (default 1): a replayed step's first launch (weight packing + step zeroing) is issued eagerly before
-# the step graph with the batch copy folded in (cv_pack_conv_weights_zero_copy); 0: the packing is the graph's first
-# node and the copy a launch of its own (A/B)
-PACK_COPY = os.environ.get("CVHIP_PACK_COPY", "1") == "1"
 
 # CVHIP_WGRAD_LANE (default 2): the deferred weight gradients of the conv / convT layers off the image (the image-side
 # layers keep their fused edge launches) on side stream 1 (Workspace.wgrad_side, cv_conv_backward_deferred_kpack_side):
@@ -156,9 +136,7 @@ PACK_COPY = os.environ.get("CVHIP_PACK_COPY", "1") == "1"
 # 1.209 -> 1.110, its fp32 twin 1.423 -> 1.330, PACS 0.869 -> 0.808, MNIST neutral (its pairs are dual grids, which
 # stay on the step's stream); 2 adds the decoder's first ConvTranspose2d (beside the latent launches): CelebA 1.928
 # -> 1.887, C3 3.581 -> 3.532, C5 1.112 -> 1.097, PACS 0.805 -> 0.800.  1: without it; 0: one stream.
-# CVHIP_WGRAD_LANES=2 (two side streams in rotation) measured neutral to slower (C5 1.112 -> 1.170 ms): default 1.
 WGRAD_LANE = int(os.environ.get("CVHIP_WGRAD_LANE", "2"))  # (2: the decoder's first ConvTranspose2d too; 1: not it)
-WGRAD_LANES = max(1, int(os.environ.get("CVHIP_WGRAD_LANES", "1")))  # side streams the weight gradients rotate over
 
 # CVHIP_SPLIT_UPDATE=1: single-process steps with side-stream weight gradients reduce and update the decoder's
 # parameters (cv_step_reduce of the decoder bucket, cv_adam_pack_step_part over the arena's decoder tail) on side
@@ -191,6 +169,31 @@ def _dist_world():
     return 1
 
 
+@dataclass
+class _StepCtx:
+    """What the program builders of one batch size share (ClearStep._context): the workspace, the step's static
+    inputs and test-injection buffers, and the placement of the latent terms resolved from the schedule switches."""
+
+    ws: Workspace
+    X: torch.Tensor
+    lab: torch.Tensor
+    eps_buf: torch.Tensor
+    perm_buf: torch.Tensor
+    gwork: torch.Tensor | None = None  # group mode: cv_group_forward's workspace and the B/m seed scale it writes
+    gscale_rec: torch.Tensor | None = None
+    tc_work: torch.Tensor | None = None  # CLEAR-TC: cv_tc_forward / cv_tc_learning_step workspace
+    bws: list | None = None  # CLEAR-MIM, branched estimator forwards: the five updates' workspaces ([0]: ws)
+    fixws: list | None = None  # ... and one in-launch split-K workspace per decoder lane
+    br_arr: object = None  # the cv_ntxent_branch array (None in group mode)
+    aux_nt: bool = False  # NT-Xent phases queued into the decoder launches (LATENT_AUX)
+    chain_nt: bool = False  # ... with the latent combine split over the rows phase and the heads backward
+    dl_nt: bool = False  # ... riding in the decoder-input launches instead of the ConvTranspose2d grids
+    det_dz: bool = False  # dz computed in fixed order by the latent combine (DET_DZ)
+    aux_args: list | None = None  # cv_ntxent_aux arguments of phases 0 and 1
+    aux_comb: tuple | None = None  # cv_ntxent_aux_combine arguments (chain_nt)
+    chain: object = None  # cv_latent_chain of the heads backward (chain_nt)
+
+
 class _AdamState:
     """Flat Adam state bound to a torch.optim.Adam over exactly the params of `arena`."""
 
@@ -210,8 +213,8 @@ class _AdamState:
                     self.v[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
                     steps = int(float(st["step"]))
         self.host_steps = steps
-        # [steps taken, arrival word, 64 group arrival words (cv_step_reduce_adam)]
-        self.step = torch.zeros(2 + 64, dtype=torch.int64, device=dev)
+        # [steps taken, arrival word] of the Adam kernels (cv_igemm.hip, cv_mi.hip)
+        self.step = torch.zeros(2, dtype=torch.int64, device=dev)
         self.step[0] = steps
         self.hyper_host = None
         self.hyper = torch.zeros(8, dtype=torch.float32, device=dev)
@@ -245,6 +248,19 @@ class _AdamState:
         if h != self.hyper_host:
             self.hyper_host = h
             self.hyper.copy_(torch.tensor(list(h) + [0.0, 0.0, 0.0], dtype=torch.float32))
+
+    def args(self):
+        """(params, grads, exp_avg, exp_avg_sq, numel, hyper, step): the leading arguments of the Adam kernels."""
+        A = self.arena
+        return (A.flat, A.grad, self.m, self.v, A.numel, self.hyper, self.step)
+
+    def adopt_host_step(self):
+        """After steps taken by the torch optimizer itself: its host step count becomes the device counter."""
+        st = self.opt.state.get(self.arena.params[0], {})
+        if "step" in st:
+            self.host_steps = int(float(st["step"]))
+            self.step.fill_(0)
+            self.step[0] = self.host_steps
 
     def sync_host(self, n_new: int):
         self.host_steps += n_new
@@ -319,8 +335,7 @@ class ClearStep:
         # the VAE's Adam launch also packs the conv weights (ADAM_PACK); _packed_sig: the parameters' version
         # counters when the packed copies were last made current (None: unknown, pack before the next replay)
         ap = ADAM_PACK
-        ap = (ap in (True, "1") or (ap not in (False, "0") and self.arena.numel >= ADAM_PACK_MIN))
-        self.adam_pack = ap and not (FUSED_ADAM and not self.dp)
+        self.adam_pack = ap in (True, "1") or (ap not in (False, "0") and self.arena.numel >= ADAM_PACK_MIN)
         self._packed_sig = None
         if self.world > 1:  # a noise stream per rank (the shards are different samples; equal noise would tie them)
             self.seed = (self.seed ^ (0x9E3779B97F4A7C15 * cvdist.rank())) & 0xFFFFFFFFFFFFFFFF
@@ -393,21 +408,11 @@ class ClearStep:
     def resync_from_host(self):
         """After steps taken outside the engine (module path / torch Adam), adopt the host counters."""
         self.sync_host_state()
-        st = self.trainer.optimizer.state.get(self.arena.params[0], {})
-        if "step" in st:
-            k = int(float(st["step"]))
-            self.adam.host_steps = k
-            self.adam.step.fill_(0)
-            self.adam.step[0] = k
+        self.adam.adopt_host_step()
         for p in self.arena.params:
             p.grad = self.arena.gview(p)
         if self.two_nets:
-            st = self.est_adam.opt.state.get(self.est_arena.params[0], {})
-            if "step" in st:
-                k = int(float(st["step"]))
-                self.est_adam.host_steps = k
-                self.est_adam.step.fill_(0)
-                self.est_adam.step[0] = k
+            self.est_adam.adopt_host_step()
 
     def sync_host_state(self):
         if self.steps_since_sync:
@@ -418,398 +423,354 @@ class ClearStep:
 
     # ----------------------------------------------------------------------------- programs
     def _programs(self, n: int):
-        sp = self.spec
-        ws = Workspace(sp, n, self.device, with_grad=True)
-        X = torch.empty(n, sp.in_ch, sp.H, sp.W, dtype=torch.float32, device=self.device)
-        lab = torch.zeros(n, dtype=torch.int64, device=self.device)
-        A = self.arena
-        hp = self.hp
-        d = sp.d
-        pg = A.gptr
-        nslot = {"mim": 6, "tc": 2}.get(self.mode, 1)
-        eps_buf = torch.zeros(nslot, n, 2 * d, dtype=torch.float32, device=self.device)  # test injection
-        perm_buf = torch.zeros(n, dtype=torch.int64, device=self.device)
-        grouped = self.mode == "group"
-        if grouped:  # segmentation / group rows of cv_group_forward, and the B/m seed scale it writes
-            gwork = torch.zeros(int(_lib.lib().cv_group_workspace_bytes(n, d)) // 4 + 4, dtype=torch.float32,
-                                device=self.device)
-            gscale_rec = torch.ones(1, dtype=torch.float32, device=self.device)
+        """The step's programs for batch size n (the keys bench.py and the tests address: tools/step_trace.py)."""
+        ctx = self._context(n)
+        fwd, fwd_inj = self._forward_program(ctx, False), self._forward_program(ctx, True)
+        pack_call, fwd_g = self._graph_forward(fwd)
+        lat, lat_inj = self._latent_programs(ctx)
+        dec, enc, enc2, upd = self._backward_update_programs(ctx)
+        # the split update (SPLIT_UPDATE): `dec_p` / `enc_p` / `upd_p` keep the one-update form for steps with a
+        # before_update hook (which reads the pre-update decoder BatchNorm)
+        dec_p, enc_p, upd_p = dec, enc, upd
+        split = (self._split_update_plan(ctx.ws, self.spec, self.arena)
+                 if SPLIT_UPDATE and self.adam_pack and ctx.ws.wgrad_side and not self.dp else None)
+        if split is not None:
+            dec, enc, enc2, upd = self._backward_update_programs(ctx, split)
+        learn = learn_inj = None
+        if self.mode == "mim":
+            learn, learn_inj = self._mim_learn_programs(ctx, False), self._mim_learn_programs(ctx, True)
+        if self.mode == "tc":
+            learn, learn_inj = self._tc_learn_program(ctx, False), self._tc_learn_program(ctx, True)
+        return dict(ws=ctx.ws, X=ctx.X, lab=ctx.lab, fwd=fwd, dec=dec, lat=lat, enc=enc, enc2=enc2, upd=upd,
+                    learn=learn, dec_p=dec_p, enc_p=enc_p, upd_p=upd_p, fwd_inj=fwd_inj, lat_inj=lat_inj,
+                    learn_inj=learn_inj, eps_buf=ctx.eps_buf, perm_buf=ctx.perm_buf, fwd_g=fwd_g, pack_call=pack_call)
 
+    def _context(self, n: int) -> _StepCtx:
+        """The buffers of batch size n and where the step's latent terms run (read from the module's schedule
+        switches now: the tests assign them before building programs)."""
+        sp, hp, d, dev = self.spec, self.hp, self.spec.d, self.device
+        ws = Workspace(sp, n, dev, with_grad=True)
+        ws.wgrad_side = WGRAD_LANE >= 1
+        ws.wgrad_side_first = WGRAD_LANE >= 2
+        nslot = {"mim": 6, "tc": 2}.get(self.mode, 1)
+        ctx = _StepCtx(ws=ws, X=torch.empty(n, sp.in_ch, sp.H, sp.W, dtype=torch.float32, device=dev),
+                       lab=torch.zeros(n, dtype=torch.int64, device=dev),
+                       eps_buf=torch.zeros(nslot, n, 2 * d, dtype=torch.float32, device=dev),  # test injection
+                       perm_buf=torch.zeros(n, dtype=torch.int64, device=dev))
+        if self.mode == "group":  # segmentation / group rows of cv_group_forward, and the B/m seed scale it writes
+            ctx.gwork = torch.zeros(int(_lib.lib().cv_group_workspace_bytes(n, d)) // 4 + 4, dtype=torch.float32,
+                                    device=dev)
+            ctx.gscale_rec = torch.ones(1, dtype=torch.float32, device=dev)
+            return ctx
+        if self.mode == "tc":
+            ctx.tc_work = torch.zeros(int(_lib.lib().cv_tc_workspace_bytes(2 * d)) // 4 + 4, dtype=torch.float32,
+                                      device=dev)
+        if self.mode == "mim" and not self.dp and MIM_BRANCHES > 0:
+            # the branched estimator forwards: own activations and statistics per update, one in-launch split-K
+            # workspace per decoder lane
+            ctx.bws = [ws] + [Workspace(sp, n, dev, with_grad=False, encoder=False) for _ in range(4)]
+            nb_fix = int(_lib.lib().cv_gemm_workspace_bytes())
+            ctx.fixws = [torch.zeros((nb_fix + 15) // 16 * 4, dtype=torch.float32, device=dev)
+                         for _ in range(MIM_BRANCHES)]
         # the contrastive branches (trainer.py:474-479): [mu_c, logvar_c] and [mu_s, logvar_s] of the heads, their
         # gradients into d(heads)
-        hb = ws.heads.data_ptr()
-        dh = ws.dheads.data_ptr()
-        branches = None
-        if not grouped:
-            alpha = float(hp["alpha"])
-            tau = float(hp["temperature"])
-            branches = [cv_ntxent_branch(hb, hb + 4 * d, 4 * d, 0, dh, dh + 4 * d, 4 * d, None, alpha,
-                                         ws.losses.data_ptr() + 12, ws.lse[0].data_ptr())]
+        hb, dh = ws.heads.data_ptr(), ws.dheads.data_ptr()
+        alpha = float(hp["alpha"])
+        branches = [cv_ntxent_branch(hb, hb + 4 * d, 4 * d, 0, dh, dh + 4 * d, 4 * d, None, alpha,
+                                     ws.losses.data_ptr() + 12, ws.lse[0].data_ptr())]
         if self.mode == "clear":
             ps = bool(hp["ps"])
             branches.append(cv_ntxent_branch(hb + 8 * d, hb + 12 * d, 4 * d, int(ps), dh + 8 * d, dh + 12 * d, 4 * d,
                                              None, alpha if ps else -alpha, ws.losses.data_ptr() + 16,
                                              ws.lse[1].data_ptr()))
-        br_arr = (cv_ntxent_branch * len(branches))(*branches) if branches is not None else None
-        # NT-Xent beside the decoder (LATENT_SIDE): CLEAR / CLEAR-MIM steps captured as one graph
-        side_nt = (LATENT_SIDE and br_arr is not None and self.mode in ("clear", "mim")
-                   and (not self.dp or self.capture_collectives))
-        aux_nt = (not side_nt and LATENT_AUX and br_arr is not None and self.mode in ("clear", "mim")
-                  and len(sp.dec) >= 3)
-        tau_c = ctypes.c_float(float(hp["temperature"])) if br_arr is not None else None
-        aux_args = ([(br_arr, len(branches), lab, n, d, self.sim, tau_c, ph, 1) for ph in (0, 1)]
-                    if aux_nt else None)
-        chain_nt = aux_nt and LATENT_CHAIN and ws.fused_heads()
+        ctx.br_arr = (cv_ntxent_branch * len(branches))(*branches)
+        if not (LATENT_AUX and self.mode in ("clear", "mim") and len(sp.dec) >= 3):
+            return ctx
+        ctx.aux_nt = True
+        ctx.aux_args = [(ctx.br_arr, len(branches), ctx.lab, n, d, self.sim, ctypes.c_float(float(hp["temperature"])),
+                         ph, 1) for ph in (0, 1)]
+        ctx.chain_nt = LATENT_CHAIN and ws.fused_heads()
         # the phases in the decoder-input launches (LATENT_AUX_DL): phase 0 queued before the forward one, phase 1
         # before the backward one (each flushed right after its launch)
-        dl_nt = (aux_nt and (LATENT_AUX_DL == 2 or (LATENT_AUX_DL == 1 and d > 8)) and not chain_nt
-                 and not LATENT_AUX_OUT and ws.fused_decoder_input())
-        hpf = lambda k, dflt: ctypes.c_float(float(hp.get(k, dflt)))
-        aux_comb = ((ws.heads, ws.z, n, d, hpf("beta", 0), hpf("loc", 0), hpf("scale", 1), self.anneal, ws.dheads,
-                     ws.losses) if chain_nt else None)
-        chain = (cv_latent_chain(ws.heads.data_ptr(), ws.z.data_ptr(), ws.dz.data_ptr(), d, ws.rec.data_ptr(),
-                                 ws.losses.data_ptr()) if chain_nt else None)
+        ctx.dl_nt = ((LATENT_AUX_DL == 2 or (LATENT_AUX_DL == 1 and d > 8)) and not ctx.chain_nt
+                     and not LATENT_AUX_OUT and ws.fused_decoder_input())
+        ctx.det_dz = DET_DZ and not ctx.chain_nt and ws.fused_decoder_input()
+        if ctx.chain_nt:
+            ctx.aux_comb = (ws.heads, ws.z, n, d, *self._kl_args(), self.anneal, ws.dheads, ws.losses)
+            ctx.chain = cv_latent_chain(ws.heads.data_ptr(), ws.z.data_ptr(), ws.dz.data_ptr(), d, ws.rec.data_ptr(),
+                                        ws.losses.data_ptr())
+        return ctx
 
-        def make_fwd(inject: bool):
-            f = Program()
-            # one launch refreshes the packed conv weights and zeroes the BN sums, the gradient arena and the
-            # two split-K / accumulated latent buffers of the step (and d(heads) when the NT-Xent gradients
-            # accumulate into it from the side stream)
-            bufs = [(ws.stats, ws.stats.numel() * 8), (A.grad, A.numel * 4), (ws.heads, ws.heads.numel() * 4),
-                    (ws.dz, ws.dz.numel() * 4)]
-            if side_nt or aux_nt:
-                bufs.append((ws.dheads, ws.dheads.numel() * 4))
-            pack_program(sp, f, "all", zero=bufs)
-            rp = None if grouped else (eps_buf[0] if inject else None, self.seed, self.offset)
-            drew = ws.encoder_program(f, X, True, zero_heads=False, reparam=rp)
-            if side_nt:  # row log-sum-exps + gradients of both branches on the side stream (joined in `lat`)
-                f.add_fork("cv_ntxent", br_arr, len(branches), lab, n, d, self.sim, ctypes.c_float(tau), 2, 1)
-                f.keep.append(br_arr)
-                f.join_at_end = False
-            if grouped:
-                hb = ws.heads.data_ptr()
-                f.add("cv_group_forward", self.group_mode, hb, hb + 4 * d, 4 * d, lab, n, d, gwork, gscale_rec,
-                      hb + 8 * d, hb + 12 * d, 4 * d, eps_buf[0] if inject else None, 2 * d, ctypes.c_uint64(self.seed),
-                      None if inject else self.offset, ws.z)
-                ws.decoder_program(f, ws.z, True, "loss", X, rec_scale=gscale_rec)
-                f.keep += [gwork, gscale_rec]
-            else:
-                ws.decoder_program(f, ws.z, True, "loss", X, reparam=None if drew else rp,
-                                   aux=None if dl_nt else aux_args, aux_combine=aux_comb,
-                                   aux_at=(0, len(sp.dec) - 1) if LATENT_AUX_OUT else None,
-                                   aux_in=aux_args[0] if dl_nt else None)
-                if aux_nt:
-                    f.keep.append(br_arr)
-            # (the running statistics are folded at the end of the backward by cv_step_reduce)
+    def _kl_args(self):
+        """(beta, loc, scale) of the annealed KL weight, as the latent kernels take them."""
+        hp = self.hp
+        return (ctypes.c_float(float(hp["beta"])), ctypes.c_float(float(hp.get("loc", 0))),
+                ctypes.c_float(float(hp.get("scale", 1))))
+
+    def _forward_program(self, ctx: _StepCtx, inject: bool) -> Program:
+        sp, ws, A, d = self.spec, ctx.ws, self.arena, self.spec.d
+        f = Program()
+        # one launch refreshes the packed conv weights and zeroes the BN sums, the gradient arena and the
+        # two split-K / accumulated latent buffers of the step (and d(heads) when the NT-Xent gradients
+        # accumulate into it before the latent combine)
+        bufs = [(ws.stats, ws.stats.numel() * 8), (A.grad, A.numel * 4), (ws.heads, ws.heads.numel() * 4),
+                (ws.dz, ws.dz.numel() * 4)]
+        if ctx.aux_nt:
+            bufs.append((ws.dheads, ws.dheads.numel() * 4))
+        pack_program(sp, f, "all", zero=bufs)
+        eps = ctx.eps_buf[0] if inject else None
+        if self.mode == "group":
+            ws.encoder_program(f, ctx.X, True, zero_heads=False)
+            hb = ws.heads.data_ptr()
+            f.add("cv_group_forward", self.group_mode, hb, hb + 4 * d, 4 * d, ctx.lab, ws.n, d, ctx.gwork,
+                  ctx.gscale_rec, hb + 8 * d, hb + 12 * d, 4 * d, eps, 2 * d, ctypes.c_uint64(self.seed),
+                  None if inject else self.offset, ws.z)
+            ws.decoder_program(f, ws.z, True, "loss", ctx.X, rec_scale=ctx.gscale_rec)
+            f.keep += [ctx.gwork, ctx.gscale_rec]
             return f
+        rp = (eps, self.seed, self.offset)
+        drew = ws.encoder_program(f, ctx.X, True, zero_heads=False, reparam=rp)
+        ws.decoder_program(f, ws.z, True, "loss", ctx.X, reparam=None if drew else rp,
+                           aux=None if ctx.dl_nt else ctx.aux_args, aux_combine=ctx.aux_comb,
+                           aux_at=(0, len(sp.dec) - 1) if LATENT_AUX_OUT else None,
+                           aux_in=ctx.aux_args[0] if ctx.dl_nt else None)
+        # (the running statistics are folded at the end of the backward by cv_step_reduce)
+        return f
 
-        fwd, fwd_inj = make_fwd(False), make_fwd(True)
-        # the replayed step's graph starts after the pack + zero launch: step() issues that launch eagerly with the
-        # batch copy into X / lab folded in (cv_pack_conv_weights_zero_copy: one launch instead of two)
+    @staticmethod
+    def _graph_forward(fwd: Program):
+        """(pack call, the rest of `fwd`): the replayed step's graph starts after the pack + zero launch, which
+        step() issues eagerly with the batch copy into X / lab folded in (cv_pack_conv_weights_zero_copy: one
+        launch instead of two)."""
         pack_call = fwd.calls[0]
         assert pack_call[0] == "cv_pack_conv_weights_zero", pack_call[0]
         fwd_g = Program()
         fwd_g.calls = fwd.calls[1:]
         fwd_g.keep = fwd.keep
-        # decoder backward (bucket 1 of the gradient arena).  Weight gradients are deferred: their split-K
-        # partial tiles, the BN affine gradients and the running statistics are reduced by one
-        # cv_step_reduce launch at the end of the backward (data parallel: one per gradient bucket, before
-        # the bucket's all-reduce)
-        dp = self.dp
-        adam_pack = self.adam_pack
-        dec_defer, enc_defer = DeferGroup(), DeferGroup()
-        ws.wgrad_side = WGRAD_LANE >= 1
-        ws.wgrad_side_first = WGRAD_LANE >= 2
-        ws.wgrad_lanes = WGRAD_LANES
-        ws._wside_next = 0
-        dec = Program()
-        det_dz = DET_DZ and (side_nt or aux_nt) and not chain_nt and ws.fused_decoder_input()
-        ws.decoder_backward_program(dec, pg, ws.dz, zero_dz=False, defer=dec_defer if dp else enc_defer,
-                                    aux_in=aux_args[1] if dl_nt else None, dz_later=det_dz)
-        if dl_nt:
-            dec.keep.append(br_arr)
-        if dp:
-            if ws.wgrad_side:
-                dec.add_join(ws.side_lanes())
-            ws.step_reduce_program(dec, dec_defer, pg, "dec", running=False)
+        return pack_call, fwd_g
 
-        # latent terms -> d(heads)
+    def _latent_programs(self, ctx: _StepCtx):
+        """(lat, lat_inj): the latent terms -> d(heads), between the decoder and the encoder backward."""
+        ws, sp, hp, d, n = ctx.ws, self.spec, self.hp, self.spec.d, ctx.ws.n
         lat = Program()
-        if grouped:
-            lat.add("cv_group_backward", self.group_mode, ws.heads, ws.z, ws.dz, gwork, n, d,
-                    ctypes.c_float(float(hp["beta"])), ctypes.c_float(float(hp.get("loc", 0))),
-                    ctypes.c_float(float(hp.get("scale", 1))), self.anneal, ws.rec, ws.dheads, ws.losses)
-            lat_inj = lat
-            lat.keep.append(gwork)
-        elif chain_nt:  # (the combine's two parts ride in the rows-phase grid and in the heads backward)
-            lat_inj = Program()
-        elif side_nt or aux_nt:
-            # (side stream: join it first) the KL + decoder-chain seed added onto the NT-Xent gradients
-            if side_nt:
-                lat.add_join()
-            if det_dz:  # (dz = d(h) W here, in fixed order, written to ws.dz for any later reader)
-                lat.add("cv_latent_combine_dz", ws.heads, ws.z, ws.gah, sp.dec_lin.weight, ws.decoder_input_geometry(),
-                        ctypes.c_float(float(hp["beta"])), ctypes.c_float(float(hp.get("loc", 0))),
-                        ctypes.c_float(float(hp.get("scale", 1))), self.anneal, ws.rec, ws.dheads, ws.losses, ws.dz,
-                        1, ws.comb_dz_work)
-            else:
-                lat.add("cv_latent_combine_acc", ws.heads, ws.z, ws.dz, n, d, ctypes.c_float(float(hp["beta"])),
-                        ctypes.c_float(float(hp.get("loc", 0))), ctypes.c_float(float(hp.get("scale", 1))),
-                        self.anneal, ws.rec, ws.dheads, ws.losses, ws.comb_work)
-            lat_inj = Program()
-            lat_inj.extend(lat)
-        if branches is not None and not side_nt and not aux_nt:
-            arr = br_arr
-            # KL + decoder chain into d(heads) with the contrastive terms accumulated on top
-            lat.add("cv_latent_step", ws.heads, ws.z, ws.dz, n, d, ctypes.c_float(float(hp["beta"])),
-                    ctypes.c_float(float(hp.get("loc", 0))), ctypes.c_float(float(hp.get("scale", 1))), self.anneal,
-                    ws.rec, ws.dheads, ws.losses, arr, len(branches), lab, self.sim, ctypes.c_float(tau))
-            lat.keep.append(arr)
-            lat_inj = Program()
-            lat_inj.extend(lat)
+        if self.mode == "group":
+            lat.add("cv_group_backward", self.group_mode, ws.heads, ws.z, ws.dz, ctx.gwork, n, d, *self._kl_args(),
+                    self.anneal, ws.rec, ws.dheads, ws.losses)
+            lat.keep.append(ctx.gwork)
+            return lat, lat
+        if ctx.chain_nt:  # (the combine's two parts ride in the rows-phase grid and in the heads backward)
+            pass
+        elif ctx.aux_nt and ctx.det_dz:
+            # the KL + decoder-chain seed added onto the NT-Xent gradients, with dz = d(h) W computed here in fixed
+            # order (written to ws.dz for any later reader)
+            lat.add("cv_latent_combine_dz", ws.heads, ws.z, ws.gah, sp.dec_lin.weight, ws.decoder_input_geometry(),
+                    *self._kl_args(), self.anneal, ws.rec, ws.dheads, ws.losses, ws.dz, 1, ws.comb_dz_work)
+        elif ctx.aux_nt:
+            lat.add("cv_latent_combine_acc", ws.heads, ws.z, ws.dz, n, d, *self._kl_args(), self.anneal, ws.rec,
+                    ws.dheads, ws.losses, ws.comb_work)
+        else:  # KL + decoder chain into d(heads) with the contrastive terms accumulated on top
+            lat.add("cv_latent_step", ws.heads, ws.z, ws.dz, n, d, *self._kl_args(), self.anneal, ws.rec, ws.dheads,
+                    ws.losses, ctx.br_arr, len(ctx.br_arr), ctx.lab, self.sim,
+                    ctypes.c_float(float(hp["temperature"])))
+        lat_inj = Program()
+        lat_inj.extend(lat)
         if self.mode == "mim":
             mlp = mlp_struct(self.est)
             zp = ws.z.data_ptr()
-            for prog, pin in ((lat, None), (lat_inj, perm_buf)):
+            for prog, pin in ((lat, None), (lat_inj, ctx.perm_buf)):
                 prog.add("cv_mi_forward", self.kind, mlp, zp, 2 * d, zp + 4 * d, 2 * d, n, pin,
                          ctypes.c_uint64(self.seed), self.offset, ws.mi_work, ws.losses.data_ptr() + 20)
                 prog.add("cv_mi_backward", self.kind, mlp, zp, 2 * d, zp + 4 * d, 2 * d, n, ws.mi_work, None,
                          ctypes.c_float(float(hp["lambda"])), None, None, 0, 1, None, ws.heads, ws.z, ws.dheads, d)
         if self.mode == "tc":  # relu(log(D/(1-D))).mean() and lambda * its gradient into d(heads)
             disc = self._disc_struct()
-            tc_work = torch.zeros(int(_lib.lib().cv_tc_workspace_bytes(2 * d)) // 4 + 4, dtype=torch.float32,
-                                  device=self.device)
             for prog in (lat, lat_inj):
                 prog.add("cv_tc_forward", disc, ws.z, n, ctypes.c_float(float(hp["lambda"])), ws.heads, ws.dheads,
-                         d, tc_work, ws.losses.data_ptr() + 20)
-        enc = Program()
-        enc2 = None
+                         d, ctx.tc_work, ws.losses.data_ptr() + 20)
+                prog.keep.append(ctx.tc_work)
+        return lat, lat_inj
+
+    def _backward_update_programs(self, ctx: _StepCtx, split=None):
+        """(dec, enc, enc2, upd): the decoder and encoder backward with their end-of-backward reductions, and the
+        optimizer step.  Weight gradients are deferred: their split-K partial tiles, the BN affine gradients and the
+        running statistics are reduced by one cv_step_reduce launch at the end of the backward (data parallel: one
+        per gradient bucket, before the bucket's all-reduce; `enc2` is the shallow encoder bucket's program, else
+        None).  split = _split_update_plan(): the split update's form of a single-process step."""
+        ws, sp, A, pg, dp = ctx.ws, self.spec, self.arena, self.arena.gptr, self.dp
+        dec_defer, enc_defer = DeferGroup(), DeferGroup()
+        one_reduce = not dp and split is None  # (the decoder's records join the encoder's: one reduction)
+        dec, enc, enc2, upd = Program(), Program(), None, Program()
+        ws.decoder_backward_program(dec, pg, ws.dz, zero_dz=False, defer=enc_defer if one_reduce else dec_defer,
+                                    aux_in=ctx.aux_args[1] if ctx.dl_nt else None, dz_later=ctx.det_dz)
+        join = ws.side_lanes()  # (the side-stream weight gradients: joined before each reduction)
+        items = sp.pack_items["enc"] + sp.pack_items["dec"]
+        adam_name = "cv_adam_pack_step" if self.adam_pack else "cv_adam_step"
+        adam_tail = (struct_array(cv_conv_pack, items), len(items)) if self.adam_pack else ()
         if dp:
+            if join:
+                dec.add_join(join)
+            ws.step_reduce_program(dec, dec_defer, pg, "dec", running=False)
             # the encoder gradients in two buckets at layer `k`: the heads and the deep convs (layers >= k, the
             # bulk of the encoder's parameters) are reduced and all-reduced as soon as their weight gradients
             # are in, while the shallow layers' backward (the big-grid GEMMs) still runs; the shallow bucket
             # follows with every layer's running statistics
-            k = self._enc_split()
-            nl = len(sp.enc)
+            k, nl = self._enc_split(), len(sp.enc)
             enc_defer2 = DeferGroup()
-            ws.encoder_backward_program(enc, pg, ws.dheads, x=X, defer=enc_defer, layers=range(nl - 1, k - 1, -1),
-                                        chain=chain)
-            if ws.wgrad_side:
-                enc.add_join(ws.side_lanes())
+            ws.encoder_backward_program(enc, pg, ws.dheads, x=ctx.X, defer=enc_defer, layers=range(nl - 1, k - 1, -1),
+                                        chain=ctx.chain)
+            if join:
+                enc.add_join(join)
             ws.step_reduce_program(enc, enc_defer, pg, ws.bn_enc[k:], running=False)
             enc2 = Program()
-            ws.encoder_backward_program(enc2, pg, ws.dheads, x=X, defer=enc_defer2, heads=False,
+            ws.encoder_backward_program(enc2, pg, ws.dheads, x=ctx.X, defer=enc_defer2, heads=False,
                                         layers=range(k - 1, -1, -1))
-            if ws.wgrad_side:
-                enc2.add_join(ws.side_lanes())
+            if join:
+                enc2.add_join(join)
             ws.step_reduce_program(enc2, enc_defer2, pg, ws.bn_enc[:k], running=False)
             ws.running_program(enc2, "all")
-        else:
-            ws.encoder_backward_program(enc, pg, ws.dheads, x=X, defer=enc_defer, chain=chain)
-        upd = Program()
-        items = sp.pack_items["enc"] + sp.pack_items["dec"]
-        pack_arr = struct_array(cv_conv_pack, items)
-        adam_name = "cv_adam_pack_step" if adam_pack else "cv_adam_step"
-        adam_tail = (pack_arr, len(items)) if adam_pack else ()
-        if dp:
-            upd.add(adam_name, A.flat, A.grad, self.adam.m, self.adam.v, A.numel, self.adam.hyper,
-                    self.adam.step, self.gscale, self.anneal, *adam_tail)
-        elif not FUSED_ADAM:
-            if ws.wgrad_side:
-                enc.add_join(ws.side_lanes())
+            upd.add(adam_name, *self.adam.args(), self.gscale, self.anneal, *adam_tail)
+        elif split is None:
+            ws.encoder_backward_program(enc, pg, ws.dheads, x=ctx.X, defer=enc_defer, chain=ctx.chain)
+            if join:
+                enc.add_join(join)
             ws.step_reduce_program(enc, enc_defer, pg, "all", running=True)
-            upd.add(adam_name, A.flat, A.grad, self.adam.m, self.adam.v, A.numel, self.adam.hyper,
-                    self.adam.step, None, self.anneal, *adam_tail)
-        else:  # single process: the optimizer step rides in the end-of-backward reduction launch
-            if ws.wgrad_side:
-                enc.add_join(ws.side_lanes())
-            ws.step_reduce_program(enc, enc_defer, pg, "all", running=True,
-                                   adam=(A.flat, A.grad, self.adam.m, self.adam.v, A.numel, self.adam.hyper,
-                                         self.adam.step, self.anneal))
-        if adam_pack:
-            upd.keep.append(pack_arr)
-        # the split update (SPLIT_UPDATE): the decoder bucket's reduction and Adam on side lane 2 once the step has
-        # read the decoder's parameters (after `lat`), beside the encoder backward; `dec_p` / `enc_p` / `upd_p` keep
-        # the one-update form for steps with a before_update hook (which reads the pre-update decoder BatchNorm)
-        dec_p, enc_p, upd_p = dec, enc, upd
-        split = self._split_update_plan(ws, sp, A) if (SPLIT_UPDATE and adam_pack and ws.wgrad_side and not dp
-                                                       and not FUSED_ADAM) else None
-        if split is not None:
+            upd.add(adam_name, *self.adam.args(), None, self.anneal, *adam_tail)
+        else:
+            # the decoder bucket's reduction and Adam on side lane 2 once the step has read the decoder's parameters
+            # (after `lat`), beside the encoder backward; the encoder's reduction and Adam part (which advances the
+            # step counters) stay at the end
             dec_off, dec_items, enc_items = split
-            dec_defer_s, enc_defer_s = DeferGroup(), DeferGroup()
-            ws._wside_next = 0
-            dec = Program()
-            ws.decoder_backward_program(dec, pg, ws.dz, zero_dz=False, defer=dec_defer_s,
-                                        aux_in=aux_args[1] if dl_nt else None, dz_later=det_dz)
-            if dl_nt:
-                dec.keep.append(br_arr)
-            enc = Program()
+            f4 = 4 * dec_off
             enc.add_join([1])  # (the decoder's weight gradients, issued on side lane 1 by the `dec` calls)
             side = Program()
-            ws.step_reduce_program(side, dec_defer_s, pg, "dec", running=True)
-            darr = struct_array(cv_conv_pack, dec_items)
-            f4 = 4 * dec_off
+            ws.step_reduce_program(side, dec_defer, pg, "dec", running=True)
             side.add("cv_adam_pack_step_part", A.flat.data_ptr() + f4, A.grad.data_ptr() + f4,
                      self.adam.m.data_ptr() + f4, self.adam.v.data_ptr() + f4, A.numel - dec_off, self.adam.hyper,
-                     self.adam.step, None, self.anneal, darr, len(dec_items), 0)
-            side.keep.append(darr)
+                     self.adam.step, None, self.anneal, struct_array(cv_conv_pack, dec_items), len(dec_items), 0)
             enc.extend(side, lane=2)
-            ws.encoder_backward_program(enc, pg, ws.dheads, x=X, defer=enc_defer_s, chain=chain)
-            enc.add_join(ws.side_lanes() + [2])
-            ws.step_reduce_program(enc, enc_defer_s, pg, ws.bn_enc, running=True)
-            upd = Program()
-            earr = struct_array(cv_conv_pack, enc_items)
+            ws.encoder_backward_program(enc, pg, ws.dheads, x=ctx.X, defer=enc_defer, chain=ctx.chain)
+            enc.add_join(join + [2])
+            ws.step_reduce_program(enc, enc_defer, pg, ws.bn_enc, running=True)
             upd.add("cv_adam_pack_step_part", A.flat, A.grad, self.adam.m, self.adam.v, dec_off, self.adam.hyper,
-                    self.adam.step, None, self.anneal, earr, len(enc_items), 1)
-            upd.keep.append(earr)
-        learn = learn_inj = None
-        if self.mode == "mim":
-            E = self.est_arena
-            mlp = mlp_struct(self.est)
-            G = cv_mlp_grad(*[E.gptr(p) for p in est_params(self.est)])
-            zp = ws.z.data_ptr()
+                    self.adam.step, None, self.anneal, struct_array(cv_conv_pack, enc_items), len(enc_items), 1)
+        return dec, enc, enc2, upd
 
-            # The 5 estimator updates (trainer.py:873-888) each run a train-mode forward of the same batch through
-            # the same (post-Adam) VAE: the encoder, its batch statistics and the heads are identical in all five,
-            # so they are computed once; each update re-runs the reparameterisation (fresh noise), the decoder
-            # (its statistics follow z) and the running-statistics update of every layer (the encoder's five
-            # momentum updates with its one set of batch statistics, as in five forwards)
-            # (the statistics of the first estimator forward are zeroed by the pack launch before it)
-            stats_zero = [(ws.stats, ws.stats.numel() * 8)]
+    # The 5 estimator updates of CLEAR-MIM (trainer.py:873-888) each run a train-mode forward of the same batch
+    # through the same (post-Adam) VAE: the encoder, its batch statistics and the heads are identical in all five,
+    # so they are computed once; each update re-runs the reparameterisation (fresh noise), the decoder (its
+    # statistics follow z) and the running-statistics update of every layer (the encoder's five momentum updates
+    # with its one set of batch statistics, as in five forwards).
+    def _mi_learning_step(self, prog: Program, ctx: _StepCtx, z: torch.Tensor, j: int, adam: bool):
+        """Estimator update j on the latents z: the learning-loss gradients, with (adam) the estimator's Adam step
+        in the same launch."""
+        ws, d, E = ctx.ws, self.spec.d, self.est_arena
+        zp = z.data_ptr()
+        G = cv_mlp_grad(*[E.gptr(p) for p in est_params(self.est)])
+        prog.add("cv_mi_learning_step", mlp_struct(self.est), zp, 2 * d, zp + 4 * d, 2 * d, ws.n, ws.mi_work,
+                 self.learn.data_ptr() + 4 * j, G,
+                 *(self.est_adam.args() if adam else (None, None, None, None, 0, None, None)))
 
-            def learn_forward(prog, j, inject):
-                rp = (eps_buf[1 + j] if inject else None, self.seed, self.offset)
+    def _mim_learn_forward(self, prog: Program, ctx: _StepCtx, j: int, inject: bool):
+        """The part of estimator forward j before its decoder pass (sequential and data-parallel forms): the encoder
+        for j = 0, else re-zeroed decoder statistics; returns the reparam the decoder pass still has to draw."""
+        ws = ctx.ws
+        rp = (ctx.eps_buf[1 + j] if inject else None, self.seed, self.offset)
+        if j == 0:
+            if ws.encoder_program(prog, ctx.X, True, reparam=rp):
+                return None  # (z drawn by the heads launch)
+        else:
+            prog.add("cv_zero_many", ptr_array([ws.dec_stats.data_ptr(), ws.dec_tickets.data_ptr()]),
+                     (ctypes.c_size_t * 2)(ws.dec_stats.numel() * 8, ws.dec_tickets.numel() * 8), 2)
+        return rp
+
+    def _mim_learn_programs(self, ctx: _StepCtx, inject: bool):
+        """CLEAR-MIM's five estimator updates after the VAE's Adam step: one Program (sequential, or with the decoder
+        forwards on side lanes: MIM_BRANCHES), or under data parallel a list of (forward + gradients, Adam) pairs
+        with the estimator gradient all-reduced in between."""
+        ws, sp, d, n = ctx.ws, self.spec, self.spec.d, ctx.ws.n
+        # the VAE Adam step just moved the weights (ADAM_PACK: and packed them); the statistics of the first
+        # estimator forward are zeroed by the same launch
+        repack = None if self.adam_pack else "all"
+        stats_zero = [(ws.stats, ws.stats.numel() * 8)]
+        if self.dp:
+            out = []
+            for j in range(5):
+                gp, ap = Program(), Program()
                 if j == 0:
-                    if ws.encoder_program(prog, X, True, reparam=rp):
-                        return None  # (z drawn by the heads launch)
-                else:
-                    prog.add("cv_zero_many", ptr_array([ws.dec_stats.data_ptr(), ws.dec_tickets.data_ptr()]),
-                             (ctypes.c_size_t * 2)(ws.dec_stats.numel() * 8, ws.dec_tickets.numel() * 8), 2)
-                return rp
-
-            def make_learn(inject: bool):
-                lp = Program()
-                # the VAE Adam step just moved the weights (ADAM_PACK: and packed them)
-                pack_program(sp, lp, None if adam_pack else "all", zero=stats_zero)
-                for j in range(5):
-                    ws.decoder_program(lp, ws.z, True, "none", reparam=learn_forward(lp, j, inject))
-                    ws.running_program(lp, "all")
-                    lp.add("cv_mi_learning_step", mlp, zp, 2 * d, zp + 4 * d, 2 * d, n, ws.mi_work,
-                           self.learn.data_ptr() + 4 * j, G, E.flat, E.grad, self.est_adam.m, self.est_adam.v,
-                           E.numel, self.est_adam.hyper, self.est_adam.step)
-                return lp
-
-            # MIM_BRANCHES > 0: the five decoder forwards are independent of each other and of the estimator (update j
-            # reads only z_j, and its decoder pass only feeds the running statistics), so once the encoder pass has
-            # run and the five z_j are drawn in order on the step's stream (the noise of the sequential form, draw by
-            # draw), update j's decoder forward runs on side lane 1 + j % MIM_BRANCHES of the graph with its own
-            # activations, statistics and in-launch split-K workspace, while the step's stream runs the five
-            # estimator learning steps (each needs only z_j and the previous step's estimator); after the join the
-            # running statistics take their five momentum updates in order, as five forwards would have.
-            nbr = MIM_BRANCHES
-            if nbr > 0:
-                bws = [ws] + [Workspace(sp, n, self.device, with_grad=False, encoder=False) for _ in range(4)]
-                nb_fix = int(_lib.lib().cv_gemm_workspace_bytes())
-                fixws = [torch.zeros((nb_fix + 15) // 16 * 4, dtype=torch.float32, device=self.device)
-                         for _ in range(nbr)]
-                dflt_fix = _lib.gemm_workspace(self.device)
-                set_fix = lambda buf: _lib.call("cv_set_gemm_workspace", buf.data_ptr(), buf.numel() * 4)  # noqa: E731
-
-            def make_learn_branched(inject: bool):
-                lp = Program()
-                # the VAE Adam step just moved the weights; the same launch zeroes every update's statistics
-                pack_program(sp, lp, None if adam_pack else "all", zero=[(w.stats, w.stats.numel() * 8) for w in bws])
-                rp = (eps_buf[1] if inject else None, self.seed, self.offset)
-                zs = [ws.z] + [w.z for w in bws[1:]]
-                if not ws.encoder_program(lp, X, True, reparam=rp):  # (z_0 drawn by the heads launch, or here)
-                    lp.add("cv_reparam_forward", ws.heads, n, d, rp[0], ctypes.c_uint64(self.seed), self.offset,
-                           zs[0], None)
-                for j in range(1, 5):
-                    lp.add("cv_reparam_forward", ws.heads, n, d, eps_buf[1 + j] if inject else None,
-                           ctypes.c_uint64(self.seed), None if inject else self.offset, zs[j], None)
-                # per lane: its decoder forwards (lanes 1..nbr) or the five learning steps (lane nbr + 1); every lane
-                # forks once, after the draws.  The calls are enqueued round-robin over the lanes, so the graph's nodes
-                # are created (and submitted at each launch) interleaved and no lane's first kernel waits behind
-                # another lane's whole chain (a multi-queue graph launch submits its nodes at ~25 us each, measured)
-                lanes = {k: [] for k in range(1, nbr + 2)}
-                for j in range(5):
-                    br = Program()
-                    bws[j].decoder_program(br, zs[j], True, "none")
-                    lp.keep += br.keep
-                    lanes[1 + j % nbr] += br.calls
-                for j in range(5):
-                    zj = zs[j].data_ptr()
-                    lp.add("cv_mi_learning_step", mlp, zj, 2 * d, zj + 4 * d, 2 * d, n, ws.mi_work,
-                           self.learn.data_ptr() + 4 * j, G, E.flat, E.grad, self.est_adam.m, self.est_adam.v,
-                           E.numel, self.est_adam.hyper, self.est_adam.step)
-                    nm, fn, a, _ = lp.calls.pop()
-                    lanes[nbr + 1].append((nm, fn, a, nbr + 1))
-                queues = {k: [(c[0], c[1], c[2], k) for c in v] for k, v in lanes.items()}
-                while any(queues.values()):
-                    for k, q in queues.items():
-                        if q:
-                            if k <= nbr:  # (each decoder lane's launches take that lane's split-K workspace)
-                                lp.add_host("gemm_workspace", set_fix, fixws[k - 1])
-                            lp.calls.append(q.pop(0))
-                lp.add_host("gemm_workspace", set_fix, dflt_fix)
-                lp.add_join()
-                ws.running_sets_program(lp, [ws.bn_enc + [bws[j].bn_1d] + bws[j].bn_dec for j in range(5)])
-                lp.keep += fixws + bws[1:]
-                return lp
-
-            def make_learn_dp(inject: bool):
-                # per estimator update: (forward + learning-loss gradients, Adam) with the estimator
-                # gradient all-reduced in between
-                out = []
-                for j in range(5):
-                    gp = Program()
-                    if j == 0:
-                        pack_program(sp, gp, None if adam_pack else "all", zero=stats_zero)
-                    ws.decoder_program(gp, ws.z, True, "none", reparam=learn_forward(gp, j, inject))
-                    ws.running_program(gp, "all")
-                    gp.add("cv_mi_learning_step", mlp, zp, 2 * d, zp + 4 * d, 2 * d, n, ws.mi_work,
-                           self.learn.data_ptr() + 4 * j, G, None, None, None, None, 0, None, None)
-                    ap = Program()
-                    ap.add("cv_adam_step", E.flat, E.grad, self.est_adam.m, self.est_adam.v, E.numel,
-                           self.est_adam.hyper, self.est_adam.step, self.gscale, None)
-                    out.append((gp, ap))
-                return out
-
-            if self.dp:
-                learn, learn_inj = make_learn_dp(False), make_learn_dp(True)
-            elif nbr > 0:
-                learn, learn_inj = make_learn_branched(False), make_learn_branched(True)
-            else:
-                learn, learn_inj = make_learn(False), make_learn(True)
-        if self.mode == "tc":
-            E = self.est_arena
-            disc = self._disc_struct()
-            G = cv_tc_grad(*[E.gptr(p) for p in E.params])
-
-            def make_tc(inject: bool):
-                # trainer.py:680-699: a second train-mode forward (fresh noise) on the updated VAE, then the
-                # discriminator's BCE gradients and its Adam step (data parallel: all-reduce in between)
-                gp = Program()
-                # the VAE Adam step just moved the weights; the same launch zeroes the forward's statistics
-                pack_program(sp, gp, None if adam_pack else "all", zero=[(ws.stats, ws.stats.numel() * 8)])
-                rp = (eps_buf[1] if inject else None, self.seed, self.offset)
-                drew = ws.encoder_program(gp, X, True, reparam=rp)
-                ws.decoder_program(gp, ws.z, True, "none", reparam=None if drew else rp)
+                    pack_program(sp, gp, repack, zero=stats_zero)
+                ws.decoder_program(gp, ws.z, True, "none", reparam=self._mim_learn_forward(gp, ctx, j, inject))
                 ws.running_program(gp, "all")
-                gp.add("cv_tc_learning_step", disc, ws.z, n, tc_work, self.learn, G)
-                ap = Program()
-                ap.add("cv_adam_step", E.flat, E.grad, self.est_adam.m, self.est_adam.v, E.numel,
-                       self.est_adam.hyper, self.est_adam.step, self.gscale if self.dp else None, None)
-                if self.dp:
-                    return [(gp, ap)]
-                gp.extend(ap)
-                return gp
+                self._mi_learning_step(gp, ctx, ws.z, j, adam=False)
+                ap.add("cv_adam_step", *self.est_adam.args(), self.gscale, None)
+                out.append((gp, ap))
+            return out
+        lp = Program()
+        if ctx.bws is None:  # the sequential form
+            pack_program(sp, lp, repack, zero=stats_zero)
+            for j in range(5):
+                ws.decoder_program(lp, ws.z, True, "none", reparam=self._mim_learn_forward(lp, ctx, j, inject))
+                ws.running_program(lp, "all")
+                self._mi_learning_step(lp, ctx, ws.z, j, adam=True)
+            return lp
+        # The branched form: the five decoder forwards are independent of each other and of the estimator (update j
+        # reads only z_j, and its decoder pass only feeds the running statistics), so once the encoder pass has
+        # run and the five z_j are drawn in order on the step's stream (the noise of the sequential form, draw by
+        # draw), update j's decoder forward runs on side lane 1 + j % nbr of the graph with its own activations,
+        # statistics and in-launch split-K workspace, while the step's stream runs the five estimator learning
+        # steps (each needs only z_j and the previous step's estimator); after the join the running statistics take
+        # their five momentum updates in order, as five forwards would have.
+        bws, fixws, nbr = ctx.bws, ctx.fixws, len(ctx.fixws)
+        set_fix = lambda buf: _lib.call("cv_set_gemm_workspace", buf.data_ptr(), buf.numel() * 4)  # noqa: E731
+        # (the same launch zeroes every update's statistics)
+        pack_program(sp, lp, repack, zero=[(w.stats, w.stats.numel() * 8) for w in bws])
+        rp = (ctx.eps_buf[1] if inject else None, self.seed, self.offset)
+        zs = [w.z for w in bws]
+        if not ws.encoder_program(lp, ctx.X, True, reparam=rp):  # (z_0 drawn by the heads launch, or here)
+            lp.add("cv_reparam_forward", ws.heads, n, d, rp[0], ctypes.c_uint64(self.seed), self.offset, zs[0], None)
+        for j in range(1, 5):
+            lp.add("cv_reparam_forward", ws.heads, n, d, ctx.eps_buf[1 + j] if inject else None,
+                   ctypes.c_uint64(self.seed), None if inject else self.offset, zs[j], None)
+        # per lane: its decoder forwards (lanes 1..nbr) or the five learning steps (lane nbr + 1); every lane
+        # forks once, after the draws.  The calls are enqueued round-robin over the lanes, so the graph's nodes
+        # are created (and submitted at each launch) interleaved and no lane's first kernel waits behind
+        # another lane's whole chain (a multi-queue graph launch submits its nodes at ~25 us each, measured)
+        lanes = {k: Program() for k in range(1, nbr + 2)}
+        for j in range(5):
+            bws[j].decoder_program(lanes[1 + j % nbr], zs[j], True, "none")
+            self._mi_learning_step(lanes[nbr + 1], ctx, zs[j], j, adam=True)
+        queues = {k: [(c[0], c[1], c[2], k) for c in P.calls] for k, P in lanes.items()}
+        while any(queues.values()):
+            for k, q in queues.items():
+                if q:
+                    if k <= nbr:  # (each decoder lane's launches take that lane's split-K workspace)
+                        lp.add_host("gemm_workspace", set_fix, fixws[k - 1])
+                    lp.calls.append(q.pop(0))
+        lp.add_host("gemm_workspace", set_fix, _lib.gemm_workspace(self.device))
+        lp.add_join()
+        ws.running_sets_program(lp, [ws.bn_enc + [bws[j].bn_1d] + bws[j].bn_dec for j in range(5)])
+        lp.keep += [P.keep for P in lanes.values()] + fixws + bws[1:]  # (the lanes' structs; the buffers in use)
+        return lp
 
-            learn, learn_inj = make_tc(False), make_tc(True)
-        return dict(ws=ws, X=X, lab=lab, fwd=fwd, dec=dec, lat=lat, enc=enc, enc2=enc2, upd=upd, learn=learn,
-                    dec_p=dec_p, enc_p=enc_p, upd_p=upd_p,
-                    fwd_inj=fwd_inj, lat_inj=lat_inj, learn_inj=learn_inj, eps_buf=eps_buf, perm_buf=perm_buf,
-                    fwd_g=fwd_g, pack_call=pack_call)
+    def _tc_learn_program(self, ctx: _StepCtx, inject: bool):
+        """trainer.py:680-699: a second train-mode forward (fresh noise) on the updated VAE, then the
+        discriminator's BCE gradients and its Adam step (data parallel: [(gradients, Adam)], all-reduce in
+        between)."""
+        ws, sp, E = ctx.ws, self.spec, self.est_arena
+        gp, ap = Program(), Program()
+        # the VAE Adam step just moved the weights; the same launch zeroes the forward's statistics
+        pack_program(sp, gp, None if self.adam_pack else "all", zero=[(ws.stats, ws.stats.numel() * 8)])
+        rp = (ctx.eps_buf[1] if inject else None, self.seed, self.offset)
+        drew = ws.encoder_program(gp, ctx.X, True, reparam=rp)
+        ws.decoder_program(gp, ws.z, True, "none", reparam=None if drew else rp)
+        ws.running_program(gp, "all")
+        gp.add("cv_tc_learning_step", self._disc_struct(), ws.z, ws.n, ctx.tc_work, self.learn,
+               cv_tc_grad(*[E.gptr(p) for p in E.params]))
+        gp.keep.append(ctx.tc_work)
+        ap.add("cv_adam_step", *self.est_adam.args(), self.gscale if self.dp else None, None)
+        if self.dp:
+            return [(gp, ap)]
+        gp.extend(ap)
+        return gp
 
     def _split_update_plan(self, ws, sp, A):
         """(decoder arena offset, decoder pack items, encoder pack items) when the decoder's parameters are the
@@ -880,28 +841,23 @@ class ClearStep:
                 seg += [("prog", [gp]), ("ar_est",), ("wait_est",), ("prog", [ap])]
         return seg
 
-    def _run_segments(self, segs, graphs=None, upd=None, before_update=None):
-        s = _lib.stream_handle()
-        gi = 0
+    def _walk(self, segs, issue, probe=True):
+        """Walk the step's segments: issue(programs) for each 'prog' segment, the bucket collectives and the waits
+        for them in between (probe: timed when comm_probe is set; not inside a capture)."""
         for item in segs:
             kind = item[0]
             if kind == "prog":
-                if graphs is None:
-                    for P in item[1]:
-                        if before_update is not None and P is upd:
-                            before_update()
-                        P.run(s)
-                else:
-                    graphs[gi].replay()
-                    gi += 1
+                issue(item[1])
             elif kind == "ar":
                 self.buckets.launch(item[1])
-            elif kind == "wait":
-                self._probe_wait(self.buckets)
             elif kind == "ar_est":
                 self.est_buckets.launch(0)
-            elif kind == "wait_est":
-                self._probe_wait(self.est_buckets)
+            else:  # "wait" / "wait_est"
+                buckets = self.buckets if kind == "wait" else self.est_buckets
+                if probe:
+                    self._probe_wait(buckets)
+                else:
+                    buckets.wait()
 
     # comm_probe: None, or a list receiving (kind, start, end) HIP events around every wait for the gradient
     # all-reduce on the step's stream: the exposed (not overlapped) collective time (bench.py)
@@ -918,12 +874,18 @@ class ClearStep:
         self.comm_probe.append(("vae" if buckets is self.buckets else "est", e0, e1))
 
     def _run_eager(self, G, inject=False, before_update=None):
-        if before_update is not None and G.get("dec_p") is not None and G["dec_p"] is not G["dec"]:
+        if before_update is not None and G["dec_p"] is not G["dec"]:
             # (the one-update programs: the hook reads the step's state before any parameter moves)
-            H = dict(G, dec=G["dec_p"], enc=G["enc_p"], upd=G["upd_p"])
-            self._run_segments(self._segments(H, inject), upd=H["upd"], before_update=before_update)
-            return
-        self._run_segments(self._segments(G, inject), upd=G["upd"], before_update=before_update)
+            G = dict(G, dec=G["dec_p"], enc=G["enc_p"], upd=G["upd_p"])
+        s = _lib.stream_handle()
+
+        def issue(progs):
+            for P in progs:
+                if before_update is not None and P is G["upd"]:
+                    before_update()
+                P.run(s)
+
+        self._walk(self._segments(G, inject), issue)
 
     def _take_injections(self, G) -> bool:
         """Consume queued test noise (cvhip.rng): eps_c, eps_s for the main forward and, in CLEAR-MIM,
@@ -948,36 +910,15 @@ class ClearStep:
         """One executable HIP graph per program segment (_lib.StepGraph: launched directly, without
         PyTorch's per-replay RNG bookkeeping); with capture_collectives, one graph for the whole data-parallel step,
         its all-reduces captured between the segments (the first, eager step has created the communicators)."""
+        def graph_of(segs):
+            return _lib.StepGraph(lambda s: self._walk(segs, lambda progs: [P.run(s) for P in progs], probe=False))
+
+        segs = self._segments(G, False, graph=True)
         if self.capture_collectives:
-            def record_all(s, segs=self._segments(G, False, graph=PACK_COPY)):
-                for item in segs:
-                    kind = item[0]
-                    if kind == "prog":
-                        for P in item[1]:
-                            P.run(s)
-                    elif kind == "ar":
-                        self.buckets.launch(item[1])
-                    elif kind == "wait":
-                        self.buckets.wait()
-                    elif kind == "ar_est":
-                        self.est_buckets.launch(0)
-                    elif kind == "wait_est":
-                        self.est_buckets.wait()
-
-            G["graphs"] = [_lib.StepGraph(record_all)]
+            G["graphs"] = [graph_of(segs)]
             G["one_graph"] = True
-            return
-        graphs = []
-        for item in self._segments(G, False, graph=PACK_COPY):
-            if item[0] != "prog":
-                continue
-
-            def record(s, progs=item[1]):
-                for P in progs:
-                    P.run(s)
-
-            graphs.append(_lib.StepGraph(record))
-        G["graphs"] = graphs
+        else:
+            G["graphs"] = [graph_of([item]) for item in segs if item[0] == "prog"]
 
     # ----------------------------------------------------------------------------- one step
     @staticmethod
@@ -1065,10 +1006,6 @@ class ClearStep:
         all-reduced under DP — and before the Adam launch; such a step runs eagerly, not from the graph (used by
         the tests to read the step's activations with the pre-update parameters)."""
         n = X.shape[0]
-        if before_update is not None and FUSED_ADAM and not self.dp:
-            # (Adam rides in the reduction launch of the `enc` program: there is no point between the complete
-            # gradients and the update at which the hook could run)
-            raise RuntimeError("before_update is not supported with CVHIP_FUSED_ADAM=1")
         G = self.graphs.get(n)
         if G is None:
             G = self._programs(n)
@@ -1081,14 +1018,15 @@ class ClearStep:
         use_graph = G["count"] >= 1 and not inject and self.graphs_enabled and before_update is None
         if use_graph and "graphs" not in G:
             self._capture(G)
-        if use_graph and PACK_COPY:
+        if use_graph:  # (the graph starts after the step's first launch, issued here with the batch copy)
             self._pack_and_load(G, X, label)
         else:
             self._load_batch(G, X, label)
         if use_graph and G.get("one_graph"):
             G["graphs"][0].replay()  # (the whole step, collectives included: one launch)
         elif use_graph:
-            self._run_segments(self._segments(G, False), G["graphs"])
+            graphs = iter(G["graphs"])
+            self._walk(self._segments(G, False), lambda progs: next(graphs).replay())
         else:
             self._run_eager(G, inject, before_update)
         G["count"] += 1

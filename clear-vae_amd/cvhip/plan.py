@@ -399,12 +399,6 @@ def ep_bwd(bnv: BNView, ey: torch.Tensor, relu: bool, stat_div: int = 1) -> cv_e
 
 
 _SIDE_STREAMS: dict = {}
-# Weight-gradient calls on a second stream: off by default.  In a replayed graph every cross-stream edge
-# costs ~10 us of idle time on both queues (rocprofv3 kernel trace of the MNIST step, round 2), and the
-# overlapped GEMMs slow each other down (each grid already fills the chip), so one stream measured as fast
-# or faster on both bench configs (MNIST 0.7015 vs 0.7046 ms, CelebA-MIM 6.46 vs 6.60 ms).
-# CVHIP_SIDE_STREAM=1 restores the two-stream schedule.
-SIDE_STREAM = os.environ.get("CVHIP_SIDE_STREAM", "0") == "1"
 
 # Operand precision of the latent-side linear layers (the four heads and the decoder Linear) under either model
 # precision: fp32.  Their fused kernels (cv_declinear.hip: cv_heads_forward / _backward,
@@ -434,16 +428,14 @@ class Program:
     Each call has a lane: 0 is the stream the program runs on; k >= 1 is side stream k.  A side call forks from the
     main stream after the main-stream calls issued before it (an event), calls of one side lane stay ordered among
     themselves, and the main stream joins every side lane it forked at the end of the program (or at an explicit
-    join).  ``add_side`` puts the backward programs' weight-gradient GEMMs on side lane 1 (CVHIP_SIDE_STREAM=1), so
-    they overlap the next layer's data-gradient GEMM instead of queueing behind it (both only read what the fork
-    point has completed); ``extend(other, lane=k)`` runs a whole program on side lane k (CLEAR-MIM's estimator decoder
-    forwards, cvhip/engine.py).  Host entries (lane HOST) call a Python function at enqueue time."""
+    join).  ``extend(other, lane=k)`` runs a whole program on side lane k (the split update's decoder reduction,
+    cvhip/engine.py); a C-ABI call may also put work on a side lane itself (cv_conv_backward_deferred_kpack_side),
+    which a later ``add_join(lanes)`` names.  Host entries (lane HOST) call a Python function at enqueue time."""
 
     def __init__(self):
         self.calls = []  # (name, fn, args, lane)
         self.keep = []  # keep ctypes structs alive
         self._events = []
-        self.join_at_end = True
 
     def _conv(self, args):
         conv = []
@@ -459,14 +451,6 @@ class Program:
 
     def add(self, name: str, *args):
         self.calls.append((name, getattr(_lib.lib(), name), self._conv(args), 0))
-
-    def add_side(self, name: str, *args):
-        self.calls.append((name, getattr(_lib.lib(), name), self._conv(args), 1 if SIDE_STREAM else 0))
-
-    def add_fork(self, name: str, *args):
-        """A call on side lane 1 regardless of CVHIP_SIDE_STREAM (it forks from the main-stream calls before
-        it; a later add_join, in this or a later program, joins it back)."""
-        self.calls.append((name, getattr(_lib.lib(), name), self._conv(args), 1))
 
     def add_join(self, lanes=()):
         """The main stream waits here for everything issued on the side lanes so far (and on `lanes`: side lanes a
@@ -485,13 +469,12 @@ class Program:
             self.calls += [(nm, fn, a, lane if isinstance(ln, int) else ln) for nm, fn, a, ln in other.calls]
         self.keep += other.keep
 
-    def run(self, stream: int | None = None, join: bool | None = None, timer: list | None = None):
-        """join=False leaves the side lanes running past the end of the program (a later program's
-        run joins them: each side lane is one ordered queue); graph capture needs a join before its end.
-        timer (eager measurement only, bench.py): a list that receives (call index, start, end) timing
+    def run(self, stream: int | None = None, timer: list | None = None):
+        """Enqueue the calls; the side lanes forked in the run are joined before it returns (graph capture needs
+        that).  timer (eager measurement only, bench.py): a list that receives (call index, start, end) timing
         events recorded around each call on the stream the call runs on."""
         try:
-            self._run(stream, join, timer)
+            self._run(stream, timer)
         except BaseException:
             # a queued NT-Xent phase (cv_ntxent_aux) whose flush this program did not reach holds this step's
             # pointers: drop it, so the next queue or served launch does not issue it
@@ -504,7 +487,7 @@ class Program:
             self._events.append(torch.cuda.Event())
         return self._events[i]
 
-    def _run(self, stream, join, timer):
+    def _run(self, stream, timer):
         s = _lib.stream_handle() if stream is None else stream
         main = torch.cuda.current_stream()
         if not any(c[3] for c in self.calls):
@@ -525,9 +508,9 @@ class Program:
 
         def join_all(extra=()):
             nonlocal ev
-            # (a join with no side lane forked in this run joins side lane 1: a fork left open by an earlier
-            # program, join_at_end=False)
-            for k in (sorted(set(active) | set(extra)) or [1]):
+            lanes = sorted(set(active) | set(extra))
+            assert lanes, "a join entry names its lanes or follows a fork of the same run"
+            for k in lanes:
                 e = self._event(ev)
                 ev += 1
                 e.record(_side_stream(main.device, k))
@@ -565,7 +548,7 @@ class Program:
             if timer is not None:
                 e1.record(st)
                 timer.append((i, e0, e1))
-        if (self.join_at_end if join is None else join) and active:
+        if active:
             join_all()
 
 
@@ -694,10 +677,8 @@ class Workspace:
         group for the step's cv_step_reduce."""
         L = _lib.lib()
         if defer is None:
-            if kind == "conv":
-                P.add_side("cv_conv_backward_weight", geom, a, b, gw, gb, 0, self.wg_work, self.wg_bytes)
-            else:
-                P.add_side("cv_linear_backward_weight", geom, a, b, gw, gb, 0, self.wg_work, self.wg_bytes)
+            name = "cv_conv_backward_weight" if kind == "conv" else "cv_linear_backward_weight"
+            P.add(name, geom, a, b, gw, gb, 0, self.wg_work, self.wg_bytes)
             return
         buf = self._defer_buf(kind, geom, key)
         name = "cv_conv_backward_weight_deferred" if kind == "conv" else "cv_linear_backward_weight_deferred"
@@ -721,12 +702,10 @@ class Workspace:
     # whose programs join side stream 1 before cv_step_reduce
     wgrad_side = False
     wgrad_side_first = False  # (also the decoder's first ConvTranspose2d, whose backward-data writes d(h))
-    wgrad_lanes = 1  # side streams the weight gradients rotate over (1, 2, ...)
-    _wside_next = 0
 
     def side_lanes(self):
         """The side lanes the weight gradients of this workspace's programs use (joined before cv_step_reduce)."""
-        return list(range(1, self.wgrad_lanes + 1)) if self.wgrad_side else []
+        return [1] if self.wgrad_side else []
 
     def _conv_backward(self, P: "Program", geom, gout, wpacked, wkpack, gin, ep, xin, gw, key, defer):
         if defer is None or not self.FUSED_EDGE_BWD:
@@ -735,10 +714,8 @@ class Workspace:
             return
         buf = self._defer_buf("conv", geom, key)
         if self.wgrad_side and min(geom.c_in, geom.c_out) > 4:
-            lane = 1 + self._wside_next % self.wgrad_lanes
-            self._wside_next += 1
             P.add("cv_conv_backward_deferred_kpack_side", geom, gout, wpacked, wkpack, gin, ep, xin, gw, None, buf,
-                  buf.numel() * 4, defer.next(), _side_stream(self.device, lane).cuda_stream)
+                  buf.numel() * 4, defer.next(), _side_stream(self.device, 1).cuda_stream)
             return
         P.add("cv_conv_backward_deferred_kpack", geom, gout, wpacked, wkpack, gin, ep, xin, gw, None, buf,
               buf.numel() * 4, defer.next())
@@ -750,20 +727,14 @@ class Workspace:
         return list(which)
 
     def step_reduce_program(self, P: "Program", defer: "DeferGroup", param_grad, which="all",
-                            running: bool = True, adam=None):
+                            running: bool = True):
         """cv_step_reduce: the group's deferred weight gradients, the BN affine gradients of `which`
-        layers and (running=True) their running statistics, in one launch.  adam = (params, grads, exp_avg,
-        exp_avg_sq, numel, hyper, step, aux_counter): cv_step_reduce_adam, the optimizer step in the same
-        launch."""
+        layers and (running=True) their running statistics, in one launch."""
         views = self._views(which)
         bns = struct_array(cv_bn, [b.cv(True) for b in views])
         dg = ptr_array([param_grad(b.mod.weight) for b in views])
         db = ptr_array([param_grad(b.mod.bias) for b in views])
         nbt = ptr_array([b.mod.num_batches_tracked.data_ptr() for b in views]) if running else None
-        if adam is not None:
-            P.add("cv_step_reduce_adam", defer.arr, defer.n, bns, len(views), dg, db, int(running),
-                  ctypes.c_float(float(views[0].mod.momentum)), nbt, *adam)
-            return
         P.add("cv_step_reduce", defer.arr, defer.n, bns, len(views), dg, db, int(running),
               ctypes.c_float(float(views[0].mod.momentum)), nbt)
 
@@ -835,14 +806,12 @@ class Workspace:
         P.add("cv_bn_update_running_sets", bns, len(views0), len(sets), ctypes.c_float(float(views0[0].mod.momentum)),
               nbt)
 
-    def running_program(self, P: Program, which="all", side: bool = False):
-        """side=True: on the side stream (only where nothing re-zeroes the statistics before a join).  which: a
-        name ('all', 'enc', 'dec') or an explicit list of BNViews (possibly of several workspaces)."""
+    def running_program(self, P: Program, which="all"):
+        """which: a name ('all', 'enc', 'dec') or an explicit list of BNViews (possibly of several workspaces)."""
         views = self._views(which)
         bns = struct_array(cv_bn, [b.cv(True) for b in views])
         nbt = ptr_array([b.mod.num_batches_tracked.data_ptr() for b in views])
-        (P.add_side if side else P.add)("cv_bn_update_running", bns, len(views),
-                                        ctypes.c_float(float(views[0].mod.momentum)), nbt)
+        P.add("cv_bn_update_running", bns, len(views), ctypes.c_float(float(views[0].mod.momentum)), nbt)
 
     # cv_decoder_input_forward / _backward (cv_declinear.hip): the reparameterisation, the decoder Linear, its
     # BatchNorm1d and ReLU in one launch, and the mask + BN1d backward + Linear weight gradient in one launch
@@ -1041,9 +1010,9 @@ class Workspace:
                 xin = operand(x, nchw=1)
             self._wgrad_call(P, "conv", g, xin, gout, param_grad(c.mod.weight), None, ("enc", li), defer)
 
-    def bn_grads_program(self, P: Program, param_grad, which: str = "all", side: bool = False):
-        views = {"all": self.bnv, "enc": self.bn_enc, "dec": [self.bn_1d] + self.bn_dec}[which]
+    def bn_grads_program(self, P: Program, param_grad, which: str = "all"):
+        views = self._views(which)
         bns = struct_array(cv_bn, [b.cv(True) for b in views])
         dg = ptr_array([param_grad(b.mod.weight) for b in views])
         db = ptr_array([param_grad(b.mod.bias) for b in views])
-        (P.add_side if side else P.add)("cv_bn_param_grads", bns, len(views), dg, db)
+        P.add("cv_bn_param_grads", bns, len(views), dg, db)

@@ -398,8 +398,7 @@ int cv_latent_combine(const float* heads, const float* z, const float* dz, int n
                       float* dheads, float* losses, double* work, cv_stream_t stream);
 /* cv_latent_combine with dheads += instead of overwritten: the fused step whose NT-Xent gradients were already
  * accumulated into a zeroed dheads — the default schedule (cvhip/engine.py LATENT_AUX: the NT-Xent phases ride in the
- * decoder's ConvTranspose2d forward grids and this call follows the decoder backward), or the opt-in side stream
- * (LATENT_SIDE, joined before this call). */
+ * decoder's ConvTranspose2d forward grids and this call follows the decoder backward). */
 int cv_latent_combine_acc(const float* heads, const float* z, const float* dz, int n, int d, float beta,
                           float loc, float scale, const int64_t* anneal_step, const double* rec_in,
                           float* dheads, float* losses, double* work, cv_stream_t stream);
@@ -614,17 +613,6 @@ int cv_adam_step(float* params, const float* grads, float* exp_avg, float* exp_a
  * (nn.BatchNorm*, momentum, unbiased running var; num_batches_tracked += 1 when nbt is given). */
 int cv_step_reduce(const cv_wgrad_defer* defers, int ndefer, const cv_bn* bn, int nbn, float* const* dgamma,
                    float* const* dbeta, int running, float momentum, int64_t* const* nbt, cv_stream_t stream);
-
-/* cv_step_reduce + cv_adam_step (no grad_scale) in the same launch, for a single-process step: every
- * gradient the reduction finalises (deferred weights / biases, dgamma, dbeta — all inside the gradient arena
- * grads[0, numel)) is stepped as soon as it is produced, the rest of the arena (its gradients already final) by
- * trailing blocks; the last block advances step[0] and aux_counter.  step: device int64[66] = (steps taken, then
- * 65 zeroed arrival words, which reset themselves).  The reduced ranges must not overlap and, with the gaps
- * between them, form at most 32 plain ranges. */
-int cv_step_reduce_adam(const cv_wgrad_defer* defers, int ndefer, const cv_bn* bn, int nbn, float* const* dgamma,
-                        float* const* dbeta, int running, float momentum, int64_t* const* nbt, float* params,
-                        float* grads, float* exp_avg, float* exp_avg_sq, int64_t numel, const float* hyper,
-                        int64_t* step, int64_t* aux_counter, cv_stream_t stream);
 
 /* BatchNorm affine gradients from the backward sums: dgamma = sum dz*xhat, dbeta = sum dz
  * (nn.BatchNorm weight/bias grads); written (not accumulated) for up to 16 layers. */
