@@ -150,11 +150,11 @@ def test_module_path_step(case):
             assert int(v) == 1, k
 
 
-def _fused_trainer(arch, zt, C, sd, hp, mode="clear", kind="CLUBSample", sim="cosine", lr=5e-4):
+def _fused_trainer(arch, zt, C, sd, hp, mode="clear", kind="CLUBSample", sim="cosine", lr=5e-4, **adam):
     from src.trainer import ClearMIMVAETrainer, CLEARVAETrainer
 
     vae = _model(arch, zt, C, sd)
-    opt = torch.optim.Adam(vae.parameters(), lr=lr)
+    opt = torch.optim.Adam(vae.parameters(), lr=lr, **adam)
     if mode == "clear":
         tr = CLEARVAETrainer(vae, opt, sim, hp, 1, torch.device("cuda"))
     else:
