@@ -147,6 +147,21 @@ class cv_mlp_grad(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4")]
 
 
+class cv_probe(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("w1", "b1", "gamma", "beta", "w2", "b2", "running_mean", "running_var",
+                                        "nbt")] + [
+        ("d", c_int),
+        ("h", c_int),
+        ("c", c_int),
+        ("eps", c_float),
+        ("momentum", c_float),
+    ]
+
+
+class cv_probe_grad(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("w1", "b1", "gamma", "beta", "w2", "b2")]
+
+
 _P = POINTER
 # name -> (restype, argtypes)
 class cv_conv_pack(ctypes.Structure):
@@ -370,6 +385,14 @@ _SIGS = {
         c_int,
         [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    "cv_probe_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "cv_probe_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cv_probe_step": (
+        c_int,
+        [_P(cv_probe), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, _P(cv_probe_grad), c_void_p, c_void_p,
+         c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    ),
+    "cv_probe_forward": (c_int, [_P(cv_probe), c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "cv_adam_step": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],

@@ -12,14 +12,16 @@ Per-step scalars that the reference reads with float() every step (trainer.py:48
 are kept on the device and copied once per epoch when the progress bar is disabled.
 ClearTCVAETrainer runs fused too (mode "tc": the factor discriminator's density-ratio
 term and its BCE step as HIP kernels), and so does HierarchicalVAETrainer (mode "group":
-the GVAE / ML-VAE group evidence as label-segmented device reductions).  The remaining trainers (CNN
-baselines, downstream probe) are outside the hot path and keep the reference's
-PyTorch loops.
+the GVAE / ML-VAE group evidence as label-segmented device reductions).  DownstreamMLPTrainer has an opt-in
+device backend (cvhip.probe.ProbeStep: the probe's step as one HIP graph).  The CNN baselines are outside the
+hot path and keep the reference's PyTorch loops.
 """
 
 from __future__ import annotations
 
 import math
+import os
+import warnings
 
 import numpy as np
 import torch
@@ -313,16 +315,49 @@ class ClearMIMVAETrainer(VAETrainer, _ClearEval):
 
 
 class DownstreamMLPTrainer(Trainer):
-    """MLP probe on mu_c of a frozen VAE (trainer.py:95-165); vae.encode runs on the HIP path."""
+    """MLP probe on mu_c of a frozen VAE (trainer.py:95-165); vae.encode runs on the HIP path.
+
+    backend: "torch" (default) trains and evaluates the probe in PyTorch, as the reference does; "device" runs each
+    training step as one HIP graph (cvhip.probe.ProbeStep: eval-mode encoder, then loss, gradients, BatchNorm running
+    statistics and Adam in cv_probe_step) and the eval forward through cv_probe_forward, for the batches the engine
+    accepts, and PyTorch for the rest.  None reads the environment variable CVHIP_PROBE (so the reference scripts
+    switch without an edit), else "torch".  A setup outside the engine's contract warns once and runs as "torch"."""
+
+    BACKENDS = ("torch", "device")
 
     def __init__(self, vae: nn.Module, model: nn.Module, optimizer: Optimizer, criterion: nn.Module,
-                 verbose_period: int, device: torch.device, transform=None) -> None:
+                 verbose_period: int, device: torch.device, transform=None, backend: str | None = None) -> None:
         super().__init__(model, optimizer, verbose_period, device, transform)
         self.criterion = criterion
         self.vae = vae
+        if backend is None:
+            backend = os.environ.get("CVHIP_PROBE") or "torch"
+        if backend not in self.BACKENDS:
+            raise ValueError(f"backend must be one of {self.BACKENDS}, got {backend!r}")
+        self.backend = backend
+        self._engine = None
+        self._engine_refused = False
+        self._resync = False
+
+    def _probe_engine(self):
+        """The device probe step, or None (backend "torch", or a setup outside its contract: warned once)."""
+        if self.backend != "device" or self._engine_refused:
+            return None
+        from cvhip.probe import ProbeStep
+
+        if self._engine is None or not self._engine.compatible():
+            if self._engine is not None:
+                self._engine.sync_host_state()
+            why = ProbeStep.unsupported_reason(self)
+            self._engine = None if why is not None else ProbeStep.build(self)
+            if self._engine is None:
+                self._engine_refused = True
+                warnings.warn(f"DownstreamMLPTrainer(backend='device') runs as 'torch': {why}", stacklevel=3)
+        return self._engine
 
     def _train(self, dataloader: DataLoader, verbose: bool, epoch_id: int):
         self.model.train()
+        engine = self._probe_engine()
         with tqdm(dataloader, unit="batch", disable=not verbose) as bar:
             bar.set_description(f"epoch {epoch_id}")
             for batch in bar:
@@ -330,6 +365,17 @@ class DownstreamMLPTrainer(Trainer):
                 X, y = X.to(self.device), y.to(self.device)
                 if self.transform:
                     X = self.transform(X)
+                if engine is not None:
+                    if engine.accepts(X):
+                        if self._resync:
+                            engine.resync_from_host()
+                            self._resync = False
+                        loss = engine.step(X, y)
+                        if verbose:
+                            bar.set_postfix(loss=float(loss))
+                        continue
+                    engine.sync_host_state()
+                    self._resync = True
                 self.optimizer.zero_grad()
                 logits = self.model(self.vae.encode(X)[0])
                 loss = self.criterion(logits, y)
@@ -337,6 +383,8 @@ class DownstreamMLPTrainer(Trainer):
                 self.optimizer.step()
                 if verbose:
                     bar.set_postfix(loss=float(loss))
+        if engine is not None:
+            engine.sync_host_state()
 
     def _valid(self, dataloader: DataLoader, verbose: bool, epoch_id: int):
         if verbose:
@@ -349,10 +397,17 @@ class DownstreamMLPTrainer(Trainer):
 
     def evaluate(self, dataloader: DataLoader, verbose: bool, epoch_id: int):
         self.model.eval()
+        engine = self._probe_engine()
         ys, logits = [], []
         with torch.no_grad():
             for batch in tqdm(dataloader, disable=not verbose, desc=f"val-epoch {epoch_id}"):
                 X, y = batch[0], batch[1].reshape(-1)
+                if engine is not None:
+                    X = X.to(self.device)
+                    if engine.accepts_eval(X):
+                        logits.append(engine.logits(X))
+                        ys.append(y)
+                        continue
                 logits.append(self.model(self.vae.encode(X.to(self.device))[0]))
                 ys.append(y)
         ys, logits = torch.cat(ys), torch.cat(logits)

@@ -597,6 +597,40 @@ size_t cv_knn_mi_workspace_bytes(int n, int d);
 int cv_knn_mi(const float* x, int ldx, int n, int d, const int32_t* cls, int k, const double* psi, int32_t* m_out,
               double* psi_sum_out, void* work, cv_stream_t stream);
 
+/* ---- downstream probe (run_styledmnist_downstream_expr.py:110-117, trainer.py:125-131): the reference's `mlp` =
+ * Linear(d,h) -> BatchNorm1d(h) -> ReLU -> Linear(h,c) on mu_c of the frozen VAE, nn.CrossEntropyLoss() defaults ----
+ * Linear weights [out][in]; running statistics are the module's own buffers (updated in place by a training step:
+ * momentum, unbiased running_var; nbt += 1 when given). */
+typedef struct cv_probe {
+  const float *w1, *b1, *gamma, *beta, *w2, *b2;   /* [h][d], [h], [h], [h], [c][h], [c] */
+  float *running_mean, *running_var;               /* [h] */
+  int64_t* nbt;                                    /* or NULL */
+  int d, h, c;
+  float eps, momentum;
+} cv_probe;
+typedef struct cv_probe_grad { float *w1, *b1, *gamma, *beta, *w2, *b2; } cv_probe_grad;
+
+/* 1 when cv_probe_step serves the shape: 2 <= n <= 1024, 1 <= d <= 64, 1 <= h <= 512, 2 <= c <= 32 */
+int cv_probe_supported(int n, int d, int h, int c);
+/* bytes of `work`: 16-byte aligned, zeroed once at allocation (its arrival counters reset themselves) */
+size_t cv_probe_workspace_bytes(int n, int h, int c);
+/* One training step of the probe in train mode (trainer.py:125-131): x [n][d] fp32 with row stride ldx >= d (mu_c:
+ * columns 0..d of the heads, ldx = 4d; rows may start at any 4-byte boundary), label [n] in [0, c) (a label outside
+ * makes the loss and its dlogits row NaN and indexes nothing).  Writes loss_out[0] = the mean cross-entropy, the
+ * gradients of W2, b2, gamma, beta, W1 (overwritten; BatchNorm column sums in fp64) and d(b1) = exact zeros (the bias
+ * feeds a train-mode BatchNorm), and updates the running statistics.  With params != NULL the same call applies
+ * torch.optim.Adam (foreach) to the whole arena (hyper / step as for cv_adam_step; the bias corrections are read on
+ * the device, step[0] += 1, step[1] stays 0): g's buffers must lie in `grads`, and each parameter of P in `params`
+ * at its gradient's offset.  params == NULL: loss + gradients only.  Two launches, no floating-point atomics: the
+ * same state and batch give the same bits.  Host validation failures return non-zero before any launch. */
+int cv_probe_step(const cv_probe* P, const float* x, int ldx, const int64_t* label, int n, void* work,
+                  float* loss_out, const cv_probe_grad* g,
+                  float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t numel,
+                  const float* hyper, int64_t* step, cv_stream_t stream);
+/* The probe in eval mode (trainer.py:146-165): logits [n][c] from the running statistics; writes nothing else.
+ * One launch; n >= 1. */
+int cv_probe_forward(const cv_probe* P, const float* x, int ldx, int n, float* logits, cv_stream_t stream);
+
 /* ---- Adam (torch.optim.Adam foreach semantics) over a flat fp32 arena ----
  * hyper: device float[8] = lr, beta1, beta2, eps, weight_decay; step: device int64[2] =
  * (steps taken, arrival counter = 0).  grad_scale (device float or NULL) multiplies the gradient
