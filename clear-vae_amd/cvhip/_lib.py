@@ -162,6 +162,19 @@ class cv_probe_grad(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("w1", "b1", "gamma", "beta", "w2", "b2")]
 
 
+class cv_cls(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("gamma", "beta", "w2", "b2", "running_mean", "running_var", "nbt")] + [
+        ("h", c_int),
+        ("c", c_int),
+        ("eps", c_float),
+        ("momentum", c_float),
+    ]
+
+
+class cv_cls_grad(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("gamma", "beta", "w2", "b2")]
+
+
 _P = POINTER
 # name -> (restype, argtypes)
 class cv_conv_pack(ctypes.Structure):
@@ -393,6 +406,13 @@ _SIGS = {
          c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     ),
     "cv_probe_forward": (c_int, [_P(cv_probe), c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "cv_cls_supported": (c_int, [c_int, c_int, c_int]),
+    "cv_cls_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cv_cls_step": (
+        c_int,
+        [_P(cv_cls), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, _P(cv_cls_grad), c_void_p],
+    ),
+    "cv_cls_forward": (c_int, [_P(cv_cls), c_void_p, c_int, c_void_p, c_void_p]),
     "cv_adam_step": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],

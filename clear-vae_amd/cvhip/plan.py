@@ -583,6 +583,45 @@ def ptr_array(ptrs):
 # ----------------------------------------------------------------------------- workspace
 
 
+def bn_arena(bns, counts, device, scalars: int = 0):
+    """The BatchNorm bookkeeping of one batch size for the layers `bns` (counts: elements per feature of each):
+    (stats, consts, views, o).  stats is the zeroed fp64 arena — per layer [REPL,2,C] forward + [REPL,2,C] backward
+    sums, then `scalars` 8-byte words at offset o, then CV_TICKET_WORDS arrival counters per layer (zeroed with the
+    statistics); consts the fp32 finalised constants (cfwd [4C], cbwd [5C] per layer, written by each layer's
+    producing launch, read by the GEMM prologues); views one BNView per layer with its slots and ticket set."""
+    tw = (_lib.TICKET_WORDS + 1) // 2  # in 8-byte words
+    tot = sum(2 * _lib.stat_repl(b.num_features) * 2 * b.num_features for b in bns) + scalars + tw * len(bns)
+    stats = torch.zeros(tot, dtype=torch.float64, device=device)
+    r4 = lambda v: (v + 3) & ~3  # noqa: E731  (16-byte aligned slots)
+    consts = torch.zeros(sum(r4(4 * b.num_features) + r4(5 * b.num_features) for b in bns), dtype=torch.float32,
+                         device=device)
+    views = []
+    o = 0
+    for b, cnt in zip(bns, counts):
+        R = _lib.stat_repl(b.num_features)
+        sz = R * 2 * b.num_features
+        st = stats[o:o + sz].view(R, 2, b.num_features)
+        gs = stats[o + sz:o + 2 * sz].view(R, 2, b.num_features)
+        views.append(BNView(b, st, gs, cnt))
+        o += 2 * sz
+    oc = 0
+    for i, bv in enumerate(views):
+        C = bv.C
+        bv.cfwd = consts[oc:oc + 4 * C]
+        bv.cbwd = consts[oc + r4(4 * C):oc + r4(4 * C) + 5 * C]
+        oc += r4(4 * C) + r4(5 * C)
+        bv.ticket = stats.data_ptr() + 8 * (o + scalars + tw * i)
+    return stats, consts, views, o
+
+
+def encoder_finalise_flags(bn_enc):
+    """Which conv-encoder layers have their BN constants finalised by the producing launch (BNView.fin_fwd /
+    fin_bwd): the layers produced and consumed by GEMM-core launches."""
+    for i, bv in enumerate(bn_enc):
+        bv.fin_fwd = i >= 1 and bv.C % 32 == 0
+        bv.fin_bwd = bv.C % 32 == 0  # (layer 0: produced by a GEMM-core bwd-data, read by the edge wgrad)
+
+
 class Workspace:
     """Device buffers of one batch size for one model (all NHWC fp32 unless noted)."""
 
@@ -603,39 +642,16 @@ class Workspace:
         # fp64 statistics arena: per BN layer [REPL,2,C] forward + [REPL,2,C] backward, plus scalars
         bns = spec.bn_layers
         counts = [n * c.h_out * c.w_out for c in spec.enc] + [n] + [n * c.h_out * c.w_out for c in spec.dec]
-        # (+ CV_TICKET_WORDS arrival counters per layer after the scalars: zeroed with the statistics)
+        self.stats, self.bn_consts, self.bnv, o = bn_arena(bns, counts, device, scalars=64)
         tw = (_lib.TICKET_WORDS + 1) // 2  # in 8-byte words
-        tot = sum(2 * _lib.stat_repl(b.num_features) * 2 * b.num_features for b in bns) + 64 + tw * len(bns)
-        self.stats = torch.zeros(tot, dtype=torch.float64, device=device)
-        # finalised BN constants (written by each layer's producing launch, read by the GEMM prologues)
-        r4 = lambda v: (v + 3) & ~3  # noqa: E731  (16-byte aligned slots)
-        self.bn_consts = torch.zeros(sum(r4(4 * b.num_features) + r4(5 * b.num_features) for b in bns), **f32)
-        self.bnv = []
-        o = 0
-        for b, cnt in zip(bns, counts):
-            R = _lib.stat_repl(b.num_features)
-            sz = R * 2 * b.num_features
-            st = self.stats[o:o + sz].view(R, 2, b.num_features)
-            gs = self.stats[o + sz:o + 2 * sz].view(R, 2, b.num_features)
-            self.bnv.append(BNView(b, st, gs, cnt))
-            o += 2 * sz
         self.scal = self.stats[o:o + 64]  # [0:REC_REPL] rec replicas (cv_output_loss), [32] mse work
-        oc = 0
-        for i, bv in enumerate(self.bnv):
-            C = bv.C
-            bv.cfwd = self.bn_consts[oc:oc + 4 * C]
-            bv.cbwd = self.bn_consts[oc + r4(4 * C):oc + r4(4 * C) + 5 * C]
-            oc += r4(4 * C) + r4(5 * C)
-            bv.ticket = self.stats.data_ptr() + 8 * (o + 64 + tw * i)
         # interior layers: produced and consumed by GEMM-core launches in both directions (the layers
         # next to the image-facing convs and the BatchNorm1d are served by the narrow / BN kernels)
         self.bn_enc = self.bnv[: len(spec.enc)]
         self.bn_1d = self.bnv[len(spec.enc)]
         self.bn_dec = self.bnv[len(spec.enc) + 1:]
         nd = len(spec.dec)
-        for i, bv in enumerate(self.bn_enc):
-            bv.fin_fwd = i >= 1 and bv.C % 32 == 0
-            bv.fin_bwd = bv.C % 32 == 0  # (layer 0: produced by a GEMM-core bwd-data, read by the edge wgrad)
+        encoder_finalise_flags(self.bn_enc)
         for j, bv in enumerate(self.bn_dec):
             bv.fin_fwd = j + 1 < nd and bv.C % 32 == 0  # (layer nd-2: read by the edge scatter / wgrad)
             bv.fin_bwd = j + 2 < nd and bv.C % 32 == 0
@@ -763,12 +779,11 @@ class Workspace:
         return (self.FUSED_HEADS_FWD and getattr(sp, "heads_wp", None) is not None
                 and bool(_lib.lib().cv_heads_forward_supported(self.n, sp.F, C, sp.d)))
 
-    def encoder_program(self, P: Program, x, train: bool, zero_heads: bool = True, reparam=None) -> bool:
-        """Encoder + heads.  reparam = (eps, seed, offset): also draw z in the heads launch when the fused heads
-        kernel serves this shape; returns True if it did (the caller then decodes z as given)."""
-        sp, n = self.spec, self.n
+    def conv_forward_program(self, P: Program, x, train: bool):
+        """The conv encoder's forwards on the NCHW image x; returns the last layer's pre-BN output (self.y_enc[-1])."""
+        n = self.n
         cur = None
-        for li, c in enumerate(sp.enc):
+        for li, c in enumerate(self.spec.enc):
             g = c.geom(n)
             if li == 0:
                 op = operand(x, nchw=1)
@@ -777,6 +792,13 @@ class Workspace:
             ep = ep_fwd(self.bn_enc[li]) if train else ep_none()
             P.add("cv_conv_forward_kpack", g, op, c.wfwd, c.wbwd, c.mod.bias, self.y_enc[li], ep)
             cur = self.y_enc[li]
+        return cur
+
+    def encoder_program(self, P: Program, x, train: bool, zero_heads: bool = True, reparam=None) -> bool:
+        """Encoder + heads.  reparam = (eps, seed, offset): also draw z in the heads launch when the fused heads
+        kernel serves this shape; returns True if it did (the caller then decodes z as given)."""
+        sp, n = self.spec, self.n
+        cur = self.conv_forward_program(P, x, train)
         # heads (Linear on the NCHW-flattened activation)
         C, Hh, Wh = sp.feat
         lin = cv_linear(n, sp.F, 4 * sp.d, Hh * Wh, C, 1, 0, LIN_MMA)

@@ -31,21 +31,22 @@ from .engine import _AdamState, _dist_world
 from .plan import ParamArena, Program, Workspace, ensure_arena, pack_program, ptr_array
 
 
-def probe_layers(model):
-    """(Linear, BatchNorm1d, ReLU, Linear) when `model` is exactly the reference's probe, else a reason string."""
+def probe_layers(model, name: str = "the probe"):
+    """(Linear, BatchNorm1d, ReLU, Linear) when `model` is exactly the reference's probe, else a reason string that
+    calls the module `name`."""
     if type(model) is not nn.Sequential or len(model) != 4:
-        return "the probe is not nn.Sequential(Linear, BatchNorm1d, ReLU, Linear)"
+        return f"{name} is not nn.Sequential(Linear, BatchNorm1d, ReLU, Linear)"
     l0, bn, act, l2 = list(model)
     if type(l0) is not nn.Linear or type(bn) is not nn.BatchNorm1d or type(act) is not nn.ReLU \
             or type(l2) is not nn.Linear:
-        return "the probe is not nn.Sequential(Linear, BatchNorm1d, ReLU, Linear)"
+        return f"{name} is not nn.Sequential(Linear, BatchNorm1d, ReLU, Linear)"
     if l0.bias is None or l2.bias is None:
-        return "a probe Linear has no bias"
+        return f"a Linear of {name} has no bias"
     if not bn.affine or not bn.track_running_stats or bn.running_mean is None \
             or not isinstance(bn.momentum, float):
-        return "the probe BatchNorm1d needs affine, track_running_stats and a float momentum"
+        return f"the BatchNorm1d of {name} needs affine, track_running_stats and a float momentum"
     if l0.out_features != bn.num_features or l2.in_features != bn.num_features:
-        return "the probe's layer widths do not chain"
+        return f"the layer widths of {name} do not chain"
     return l0, bn, act, l2
 
 

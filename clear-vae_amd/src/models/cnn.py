@@ -1,5 +1,6 @@
-"""Baseline CNN classifiers (reference code/src/models/cnn.py).  Comparison baselines, outside the
-CLEAR-VAE hot path: plain PyTorch modules kept so the experiment scripts import."""
+"""Baseline CNN classifiers (reference code/src/models/cnn.py): plain PyTorch modules with the reference's module
+tree and state_dict keys.  SimpleCNNTrainer(backend="device") trains SimpleCNNClassifier / SimpleCNN64Classifier on
+the HIP kernels (cvhip.cnn.CnnStep reads this module tree); the LAM classifiers stay PyTorch."""
 
 import torch.nn as nn
 

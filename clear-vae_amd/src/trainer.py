@@ -13,8 +13,9 @@ are kept on the device and copied once per epoch when the progress bar is disabl
 ClearTCVAETrainer runs fused too (mode "tc": the factor discriminator's density-ratio
 term and its BCE step as HIP kernels), and so does HierarchicalVAETrainer (mode "group":
 the GVAE / ML-VAE group evidence as label-segmented device reductions).  DownstreamMLPTrainer has an opt-in
-device backend (cvhip.probe.ProbeStep: the probe's step as one HIP graph).  The CNN baselines are outside the
-hot path and keep the reference's PyTorch loops.
+device backend (cvhip.probe.ProbeStep: the probe's step as one HIP graph), and so does SimpleCNNTrainer
+(cvhip.cnn.CnnStep: conv trunk, classifier tail, backward and Adam as one HIP graph).  LAMCNNTrainer keeps the
+reference's PyTorch loop.
 """
 
 from __future__ import annotations
@@ -415,23 +416,77 @@ class DownstreamMLPTrainer(Trainer):
 
 
 class SimpleCNNTrainer(Trainer):
+    """The CNN baseline (trainer.py:168-233).
+
+    backend: "torch" (default) trains and evaluates in PyTorch, as the reference does; "device" runs each training
+    step as one HIP graph (cvhip.cnn.CnnStep: the conv trunk on the VAE encoder's kernels, the classifier tail in
+    cv_cls_step, one Adam launch over a flat arena) and the eval forward through cv_cls_forward, for the batches the
+    engine accepts, and PyTorch for the rest.  None reads the environment variable CVHIP_CNN (so the reference scripts
+    switch without an edit), else "torch".  A setup outside the engine's contract warns once and runs as "torch"."""
+
+    BACKENDS = ("torch", "device")
+
     def __init__(self, model: nn.Module, optimizer: Optimizer, criterion: nn.Module, verbose_period: int,
-                 device: torch.device, transform=None) -> None:
+                 device: torch.device, transform=None, backend: str | None = None) -> None:
         super().__init__(model, optimizer, verbose_period, device, transform)
         self.criterion = criterion
+        if backend is None:
+            backend = os.environ.get("CVHIP_CNN") or "torch"
+        if backend not in self.BACKENDS:
+            raise ValueError(f"backend must be one of {self.BACKENDS}, got {backend!r}")
+        self.backend = backend
+        self._engine = None
+        self._engine_refused = False
+        self._resync = False
+
+    def _cnn_engine(self):
+        """The device CNN step, or None (backend "torch", or a setup outside its contract: warned once)."""
+        if self.backend != "device" or self._engine_refused:
+            return None
+        from cvhip.cnn import CnnStep
+
+        if self._engine is None or not self._engine.compatible():
+            if self._engine is not None:
+                self._engine.sync_host_state()
+            why = CnnStep.unsupported_reason(self)
+            self._engine = None if why is not None else CnnStep.build(self)
+            if self._engine is None:
+                self._engine_refused = True
+                warnings.warn(f"{type(self).__name__}(backend='device') runs as 'torch': {why}", stacklevel=3)
+        return self._engine
+
+    def invalidate_packed(self):
+        """Call after writing parameters through `.data` (which bypasses their version counters): the device backend
+        repacks its conv weights before the next step.  No effect under backend "torch" or before the first step."""
+        if self._engine is not None:
+            self._engine.invalidate_packed()
 
     def _train(self, dataloader: DataLoader, verbose: bool, epoch_id: int):
         self.model.train()
+        engine = self._cnn_engine()
         with tqdm(dataloader, unit="batch", disable=not verbose) as bar:
             bar.set_description(f"epoch {epoch_id}")
             for batch in bar:
                 X, y = _batch(batch, self.device, self.transform)
+                if engine is not None:
+                    if engine.accepts(X):
+                        if self._resync:
+                            engine.resync_from_host()
+                            self._resync = False
+                        loss = engine.step(X, y)
+                        if verbose:
+                            bar.set_postfix(loss=float(loss))
+                        continue
+                    engine.sync_host_state()
+                    self._resync = True
                 self.optimizer.zero_grad()
                 loss = self.criterion(self.model(X), y)
                 loss.backward()
                 self.optimizer.step()
                 if verbose:
                     bar.set_postfix(loss=float(loss))
+        if engine is not None:
+            engine.sync_host_state()
 
     def _valid(self, dataloader: DataLoader, verbose: bool, epoch_id: int):
         if verbose:
@@ -444,20 +499,28 @@ class SimpleCNNTrainer(Trainer):
 
     def evaluate(self, dataloader: DataLoader, verbose: bool, epoch_id: int):
         self.model.eval()
+        engine = self._cnn_engine()
         ys, logits = [], []
         with torch.no_grad():
             for batch in tqdm(dataloader, disable=not verbose, desc=f"val-epoch {epoch_id}"):
                 X, y = batch[0], batch[1].reshape(-1)
-                logits.append(self.model(X.to(self.device)))
+                X = X.to(self.device)
+                if engine is not None and engine.accepts_eval(X):
+                    logits.append(engine.logits(X))
+                else:
+                    logits.append(self.model(X))
                 ys.append(y)
         ys, logits = torch.cat(ys), torch.cat(logits)
         return auc(logits, ys), accurary(logits, ys)
 
 
 class LAMCNNTrainer(SimpleCNNTrainer):
+    """backend is accepted and passed through, but the LAM step (three trunk forwards and lam_loss) always trains in
+    PyTorch, and the LAM classifiers are outside the device engine's contract, so evaluate() stays PyTorch too."""
+
     def __init__(self, model: nn.Module, optimizer: Optimizer, criterion: nn.Module, hyperparameter: dict,
-                 verbose_period: int, device: torch.device, transform=None) -> None:
-        super().__init__(model, optimizer, criterion, verbose_period, device, transform)
+                 verbose_period: int, device: torch.device, transform=None, backend: str | None = None) -> None:
+        super().__init__(model, optimizer, criterion, verbose_period, device, transform, backend)
         self.hyperparameter = hyperparameter
 
     def ss_pairing(self, x, y):

@@ -36,11 +36,11 @@ def _resolve(name):
 
 
 def get_cnn_trainer(n_class, device, cnn_arch: str = "SimpleCNNClassifier", in_channel: int = 1,
-                    verbose_period: int = 5):
+                    verbose_period: int = 5, backend=None):
     cnn = _resolve(cnn_arch)(n_class=n_class, in_channel=in_channel).to(device)
     optimizer = torch.optim.Adam(cnn.parameters(), lr=1e-4)
     return SimpleCNNTrainer(cnn, optimizer, torch.nn.CrossEntropyLoss(), verbose_period=verbose_period,
-                            device=device)
+                            device=device, backend=backend)
 
 
 def get_lamcnn_trainer(n_class, device, lam_coef, cnn_arch: str = "LAMCNNClassifier", in_channel: int = 1,

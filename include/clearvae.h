@@ -631,6 +631,38 @@ int cv_probe_step(const cv_probe* P, const float* x, int ldx, const int64_t* lab
  * One launch; n >= 1. */
 int cv_probe_forward(const cv_probe* P, const float* x, int ldx, int n, float* logits, cv_stream_t stream);
 
+/* ---- CNN baseline, the classifier tail (code/src/models/cnn.py:22-27: cls_head[1:] = BatchNorm1d(h) -> ReLU ->
+ * Linear(h,c); code/src/trainer.py:196-199 the training step's loss and backward, :228 the eval forward) ----
+ * `a` [n][h] row-major is the output of cls_head[0] = Linear(2048, h), bias included.  Linear weight [c][h]; the
+ * running statistics are the module's own buffers. */
+typedef struct cv_cls {
+  const float *gamma, *beta, *w2, *b2;      /* [h], [h], [c][h], [c] */
+  float *running_mean, *running_var;        /* [h] */
+  int64_t* nbt;                             /* or NULL */
+  int h, c; float eps, momentum;
+} cv_cls;
+typedef struct cv_cls_grad { float *gamma, *beta, *w2, *b2; } cv_cls_grad;
+
+/* 1 when cv_cls_step serves the shape: 2 <= n <= 1024, 1 <= h <= 512, 2 <= c <= 32 */
+int cv_cls_supported(int n, int h, int c);
+/* bytes of `work` (a positive multiple of 16): 16-byte aligned, zeroed once at allocation; its arrival counters (the
+ * first 64 bytes) reset themselves, so they read zero again after every call */
+size_t cv_cls_workspace_bytes(int n, int h, int c);
+/* One training step of the tail in train mode (cnn.py:22-27 under trainer.py:196-199): BatchNorm1d with batch mean
+ * and biased variance (fp64 column sums), running_mean/var <- (1-m) old + m (mean, unbiased variance), nbt += 1 when
+ * given; y = ReLU(gamma xhat + beta), logits = y W2^T + b2; loss_out[0] = the mean cross-entropy (stable
+ * log-softmax); label [n] in [0, c) (a label outside makes the loss and its dlogits row NaN and indexes nothing).
+ * Writes (overwritten, not accumulated) g->w2 = dlogits^T y, g->b2, g->gamma, g->beta (fp64 column sums) and
+ * da [n][h] = gamma istd (dy_m - dbeta/n - xhat dgamma/n), the gradient handed back to cls_head[0].  No optimizer
+ * inside.  Two launches, no floating-point atomics, no workgroup waits for another: the same state and batch give
+ * the same bits.  Host validation failures return non-zero before any launch. */
+int cv_cls_step(const cv_cls* P, const float* a, const int64_t* label, int n, void* work, float* loss_out,
+                float* da, const cv_cls_grad* g, cv_stream_t stream);
+/* The tail in eval mode (trainer.py:228 under model.eval()): logits [n][c] from the running statistics; writes
+ * nothing else.  One launch; any n >= 1 (rows are independent: the batch limit of cv_cls_step does not apply), h and c
+ * as for cv_cls_supported. */
+int cv_cls_forward(const cv_cls* P, const float* a, int n, float* logits, cv_stream_t stream);
+
 /* ---- Adam (torch.optim.Adam foreach semantics) over a flat fp32 arena ----
  * hyper: device float[8] = lr, beta1, beta2, eps, weight_decay; step: device int64[2] =
  * (steps taken, arrival counter = 0).  grad_scale (device float or NULL) multiplies the gradient
