@@ -175,6 +175,15 @@ class cv_cls_grad(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("gamma", "beta", "w2", "b2")]
 
 
+class cv_lam(ctypes.Structure):
+    _fields_ = [("w", c_void_p), ("b", c_void_p), ("lam", c_void_p), ("c", c_int), ("in_ch", c_int),
+                ("in_pix", c_int)]
+
+
+class cv_lam_grad(ctypes.Structure):
+    _fields_ = [("w", c_void_p), ("b", c_void_p)]
+
+
 _P = POINTER
 # name -> (restype, argtypes)
 class cv_conv_pack(ctypes.Structure):
@@ -413,6 +422,15 @@ _SIGS = {
         [_P(cv_cls), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, _P(cv_cls_grad), c_void_p],
     ),
     "cv_cls_forward": (c_int, [_P(cv_cls), c_void_p, c_int, c_void_p, c_void_p]),
+    "cv_lam_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "cv_lam_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "cv_lam_pair": (c_int, [c_void_p, c_int, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "cv_lam_step": (
+        c_int,
+        [_P(cv_lam), c_void_p, _P(cv_bn), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+         _P(cv_lam_grad), c_void_p],
+    ),
+    "cv_lam_forward": (c_int, [_P(cv_lam), c_void_p, _P(cv_bn), c_int, c_void_p, c_void_p]),
     "cv_adam_step": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],

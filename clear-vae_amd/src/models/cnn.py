@@ -1,6 +1,7 @@
 """Baseline CNN classifiers (reference code/src/models/cnn.py): plain PyTorch modules with the reference's module
 tree and state_dict keys.  SimpleCNNTrainer(backend="device") trains SimpleCNNClassifier / SimpleCNN64Classifier on
-the HIP kernels (cvhip.cnn.CnnStep reads this module tree); the LAM classifiers stay PyTorch."""
+the HIP kernels (cvhip.cnn.CnnStep reads this module tree), LAMCNNTrainer(backend="device") the LAM classifiers
+(cvhip.lam.LamStep)."""
 
 import torch.nn as nn
 

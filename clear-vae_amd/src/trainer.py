@@ -14,8 +14,9 @@ ClearTCVAETrainer runs fused too (mode "tc": the factor discr
 term and its BCE step as HIP kernels), and so does HierarchicalVAETrainer (mode "group":
 the GVAE / ML-VAE group evidence as label-segmented device reductions).  DownstreamMLPTrainer has an opt-in
 device backend (cvhip.probe.ProbeStep: the probe's step as one HIP graph), and so does SimpleCNNTrainer
-(cvhip.cnn.CnnStep: conv trunk, classifier tail, backward and Adam as one HIP graph).  LAMCNNTrainer keeps the
-reference's PyTorch loop.
+(cvhip.cnn.CnnStep: conv trunk, classifier tail, backward and Adam as one HIP graph) and LAMCNNTrainer
+(cvhip.lam.LamStep: the reference's three trunk forwards as one, the LAM tail in cv_lam_step, backward and Adam as
+one HIP graph).
 """
 
 from __future__ import annotations
@@ -439,17 +440,23 @@ class SimpleCNNTrainer(Trainer):
         self._engine_refused = False
         self._resync = False
 
+    @staticmethod
+    def _step_class():
+        from cvhip.cnn import CnnStep
+
+        return CnnStep
+
     def _cnn_engine(self):
-        """The device CNN step, or None (backend "torch", or a setup outside its contract: warned once)."""
+        """The device step, or None (backend "torch", or a setup outside its contract: warned once)."""
         if self.backend != "device" or self._engine_refused:
             return None
-        from cvhip.cnn import CnnStep
+        Step = self._step_class()
 
         if self._engine is None or not self._engine.compatible():
             if self._engine is not None:
                 self._engine.sync_host_state()
-            why = CnnStep.unsupported_reason(self)
-            self._engine = None if why is not None else CnnStep.build(self)
+            why = Step.unsupported_reason(self)
+            self._engine = None if why is not None else Step.build(self)
             if self._engine is None:
                 self._engine_refused = True
                 warnings.warn(f"{type(self).__name__}(backend='device') runs as 'torch': {why}", stacklevel=3)
@@ -515,13 +522,25 @@ class SimpleCNNTrainer(Trainer):
 
 
 class LAMCNNTrainer(SimpleCNNTrainer):
-    """backend is accepted and passed through, but the LAM step (three trunk forwards and lam_loss) always trains in
-    PyTorch, and the LAM classifiers are outside the device engine's contract, so evaluate() stays PyTorch too."""
+    """The LAM baseline (trainer.py:236-288).
+
+    backend: "torch" (default) is the reference's loop (three train-mode trunk forwards and lam_loss per step);
+    "device" runs each training step as one HIP graph (cvhip.lam.LamStep: one trunk forward, the LAM tail in
+    cv_lam_step, one trunk backward, three running-statistics updates, one Adam launch) and the eval forward through
+    cv_lam_forward, for the batches the engine accepts, and PyTorch for the rest.  The device pairing is drawn by
+    cv_lam_pair from the device Philox stream (keyed by torch.initial_seed()), not from torch.randperm.  None reads
+    CVHIP_CNN, else "torch".  A setup outside the engine's contract warns once and runs as "torch"."""
 
     def __init__(self, model: nn.Module, optimizer: Optimizer, criterion: nn.Module, hyperparameter: dict,
                  verbose_period: int, device: torch.device, transform=None, backend: str | None = None) -> None:
         super().__init__(model, optimizer, criterion, verbose_period, device, transform, backend)
         self.hyperparameter = hyperparameter
+
+    @staticmethod
+    def _step_class():
+        from cvhip.lam import LamStep
+
+        return LamStep
 
     def ss_pairing(self, x, y):
         """Stratified shuffle: every sample is paired with a random sample of the same label
@@ -537,6 +556,9 @@ class LAMCNNTrainer(SimpleCNNTrainer):
         """(X, y) batches, as the reference's callers pass them (trainer.py:259-288)."""
         cnn = self.model
         cnn.train()
+        engine = self._cnn_engine()
+        if engine is not None:
+            return self._train_device(engine, dataloader, verbose, epoch_id)
         lam_coef = self.hyperparameter["lam_coef"]
         with tqdm(dataloader, unit="batch", disable=not verbose) as bar:
             bar.set_description(f"epoch {epoch_id}")
@@ -550,6 +572,36 @@ class LAMCNNTrainer(SimpleCNNTrainer):
                 loss.backward()
                 self.optimizer.step()
                 bar.set_postfix(ce_loss=float(loss_ce), lam_loss=float(loss_lam))
+
+    def _train_device(self, engine, dataloader: DataLoader, verbose: bool, epoch_id: int):
+        """The same epoch with the device step for the batches it accepts; a refused batch takes the loop above's step
+        in PyTorch (the sync_host_state / resync dance of SimpleCNNTrainer._train).  The two postfix reads
+        synchronise, so they happen only when the bar is enabled."""
+        cnn = self.model
+        with tqdm(dataloader, unit="batch", disable=not verbose) as bar:
+            bar.set_description(f"epoch {epoch_id}")
+            for batch in bar:
+                X, y = _batch(batch, self.device, self.transform)
+                if engine.accepts(X):
+                    if self._resync:
+                        engine.resync_from_host()
+                        self._resync = False
+                    losses = engine.step(X, y)
+                    if verbose:
+                        bar.set_postfix(ce_loss=float(losses[0]), lam_loss=float(losses[1]))
+                    continue
+                engine.sync_host_state()
+                self._resync = True
+                X_tilde = self.ss_pairing(X, y)
+                self.optimizer.zero_grad()
+                loss_ce = self.criterion(cnn(X), y)
+                loss_lam = lam_loss(cnn.net(X), cnn.net(X_tilde), y, cnn.cls_head.weight)
+                loss = loss_ce + self.hyperparameter["lam_coef"] * loss_lam
+                loss.backward()
+                self.optimizer.step()
+                if verbose:
+                    bar.set_postfix(ce_loss=float(loss_ce), lam_loss=float(loss_lam))
+        engine.sync_host_state()
 
 
 class HierarchicalVAETrainer(VAETrainer):

@@ -44,11 +44,11 @@ def get_cnn_trainer(n_class, device, cnn_arch: str = "SimpleCNNClassifier", in_c
 
 
 def get_lamcnn_trainer(n_class, device, lam_coef, cnn_arch: str = "LAMCNNClassifier", in_channel: int = 1,
-                       verbose_period: int = 5):
+                       verbose_period: int = 5, backend=None):
     cnn = _resolve(cnn_arch)(n_class=n_class, in_channel=in_channel).to(device)
     optimizer = torch.optim.Adam(cnn.parameters(), lr=1e-4)
     return LAMCNNTrainer(cnn, optimizer, torch.nn.CrossEntropyLoss(), {"lam_coef": lam_coef},
-                         verbose_period=verbose_period, device=device)
+                         verbose_period=verbose_period, device=device, backend=backend)
 
 
 def get_hierarchical_vae_trainer(beta, vae_lr, z_dim, group_mode, device, vae_arch: str = "VAE",

@@ -663,6 +663,54 @@ int cv_cls_step(const cv_cls* P, const float* a, const int64_t* label, int n, vo
  * as for cv_cls_supported. */
 int cv_cls_forward(const cv_cls* P, const float* a, int n, float* logits, cv_stream_t stream);
 
+/* ---- LAM baseline, the tail (code/src/models/cnn.py:57-66: cls_head = Linear(2048, c) on the flattened trunk;
+ * code/src/trainer.py:259-288 the training step, :249-257 ss_pairing; code/src/losses.py:173-187 lam_loss) ----
+ * The reference's three train-mode trunk forwards per step (cnn(X), cnn.net(X), cnn.net(X[pair])) are one: batch
+ * statistics do not see row order, so net(X[pair]) = net(X)[pair].  With h = ReLU(BN(y)) [n][F] the flattened trunk
+ * output, p = pair, q = pair^-1 and lambda = *lam:
+ *   logits = h W^T + b;  ce = mean cross-entropy;  dlogits = (softmax - onehot) / n
+ *   lam = (1/n) sum_i sum_f ((h[i,f] - h[p_i,f]) W[y_i,f])^2                 (the trainer's loss is ce + lambda lam)
+ *   gb[k] = sum_i dlogits[i,k]
+ *   gW[k,f] = sum_i dlogits[i,k] h[i,f] + lambda (2/n) W[k,f] sum_{i: y_i = k} (h[i,f] - h[p_i,f])^2
+ *   dh[i,f] = sum_k dlogits[i,k] W[k,f]
+ *             + lambda (2/n) (W[y_i,f]^2 (h[i,f] - h[p_i,f]) - W[y_q,f]^2 (h[q,f] - h[i,f])),  q = q_i
+ * (right for any permutation, label-preserving or not).  w [c][F] is in PyTorch feature order f = ch * in_pix + p;
+ * y and gin are in storage order [n][in_pix][in_ch].  lam is a DEVICE float the caller rewrites when the
+ * hyperparameter changes (a replayed graph sees the change). */
+typedef struct cv_lam {
+  const float *w, *b;   /* [c][in_ch * in_pix], [c] */
+  const float* lam;     /* device float: lam_coef */
+  int c, in_ch, in_pix;
+} cv_lam;
+typedef struct cv_lam_grad { float *w, *b; } cv_lam_grad;
+
+/* 1 when cv_lam_step serves the shape: 2 <= n <= 1024, in_ch >= 1, 1 <= in_pix <= 16, in_ch * in_pix <= 2048,
+ * 2 <= c <= 32 (both reference trunks: 128 channels x 16 pixels and 512 x 4) */
+int cv_lam_supported(int n, int in_ch, int in_pix, int c);
+/* bytes of `work` (a positive multiple of 16; 0 for an unsupported shape): 16-byte aligned, zeroed once at
+ * allocation; its arrival counter (the first 64 bytes) resets itself, so it reads zero again after every call */
+size_t cv_lam_workspace_bytes(int n, int in_ch, int in_pix, int c);
+/* The device ss_pairing (trainer.py:249-257): pair_out [n] = a uniformly random permutation inside each label
+ * stratum (label[pair[i]] == label[i]; any int64 labels, they only compare), 1 <= n <= 1024, one workgroup.  The
+ * Philox keys come from (seed, *offset); *offset (device, or NULL = 0) is advanced by one afterwards, so a replayed
+ * graph draws a fresh pairing each time and the same (seed, offset, label) gives the same pair. */
+int cv_lam_pair(const int64_t* label, int n, uint64_t seed, uint64_t* offset, int64_t* pair_out, cv_stream_t stream);
+/* One training step of the tail.  y: the last conv block's pre-BN output; bn: that block's BatchNorm2d in train mode
+ * with its forward sums (count = n * in_pix; finalised cfwd constants are used when bn->ticket[0] says so, else the
+ * replicas are folded, as cv_heads_backward).  label [n] in [0, c); pair [n] a permutation of [0, n) (the kernel
+ * builds its inverse).  Writes loss_out[0] = ce, loss_out[1] = lam (unscaled), g->w, g->b (overwritten),
+ * gin [n][F] = dh [BN(y) > 0] and the complete backward sums (sum dz, sum dz xhat; fp64) into replica 0 of
+ * gstat_out [CV_STAT_REPL(C)][2][C] (the other replicas are left as they are: zeroed by the step).  bn->ticket is
+ * left untouched (zero), so consumers fold the sums themselves.  A label outside [0, c), a pair entry outside
+ * [0, n) or a pair that is no permutation makes both losses NaN and indexes nothing.  Two launches, no
+ * floating-point atomics, no workgroup waits for another: the same state and batch give the same bits.  Host
+ * validation failures return non-zero before any launch. */
+int cv_lam_step(const cv_lam* P, const float* y, const cv_bn* bn, const int64_t* label, const int64_t* pair, int n,
+                void* work, float* loss_out, float* gin, double* gstat_out, const cv_lam_grad* g, cv_stream_t stream);
+/* The tail in eval mode (trainer.py:215-233 under model.eval()): logits [n][c] with bn as given (train = 0: running
+ * statistics); writes nothing else.  One launch; any n >= 1; the other limits as for cv_lam_supported. */
+int cv_lam_forward(const cv_lam* P, const float* y, const cv_bn* bn, int n, float* logits, cv_stream_t stream);
+
 /* ---- Adam (torch.optim.Adam foreach semantics) over a flat fp32 arena ----
  * hyper: device float[8] = lr, beta1, beta2, eps, weight_decay; step: device int64[2] =
  * (steps taken, arrival counter = 0).  grad_scale (device float or NULL) multiplies the gradient
