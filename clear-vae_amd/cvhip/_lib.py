@@ -407,6 +407,12 @@ _SIGS = {
         c_int,
         [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    "cv_rank_auc_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "cv_rank_auc": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p],
+    ),
     "cv_probe_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "cv_probe_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cv_probe_step": (

@@ -7,7 +7,7 @@ The pairwise_* / snn_loss / logsumexp helpers keep the reference's tensor-level 
 callers that use them directly (they are building blocks, not the trained path); the supcon / lam
 losses and the sklearn metrics are outside the hot path and stay as in the
 reference (sklearn on CPU); gMIG also has a device backend (cv_knn_mi through cvhip.metrics), chosen
-per call or with the environment variable CVHIP_GMIG.
+per call or with the environment variable CVHIP_GMIG, and so does auc (cv_rank_auc, CVHIP_AUC).
 """
 
 from __future__ import annotations
@@ -55,7 +55,22 @@ def accurary(logit: torch.Tensor, y: torch.Tensor):
     return (yh.view(-1) == y.view(-1)).float().mean()
 
 
-def auc(logit: torch.Tensor, y: torch.Tensor):
+AUC_BACKENDS = ("sklearn", "device")
+
+
+def auc(logit: torch.Tensor, y: torch.Tensor, backend=None):
+    """Per-class average precision and AUROC (losses.py:24-33).  backend "sklearn" (the default) is the reference's
+    computation: sklearn on host copies of the softmax.  "device" computes the same rank statistics as a HIP kernel
+    (cvhip.metrics.auc) on the logits where they are.  backend=None takes the environment variable CVHIP_AUC when
+    it is set, else "sklearn"."""
+    if backend is None:
+        backend = os.environ.get("CVHIP_AUC") or "sklearn"
+    if backend not in AUC_BACKENDS:
+        raise ValueError(f"auc: unknown backend {backend!r} (one of {', '.join(AUC_BACKENDS)})")
+    if backend == "device":
+        from cvhip import metrics as _metrics
+
+        return _metrics.auc(logit, y)
     num_classes = int(y.max() + 1)
     ph = logit.softmax(dim=1).detach().cpu()
     y = y.cpu()

@@ -597,6 +597,24 @@ size_t cv_knn_mi_workspace_bytes(int n, int d);
 int cv_knn_mi(const float* x, int ldx, int n, int d, const int32_t* cls, int k, const double* psi, int32_t* m_out,
               double* psi_sum_out, void* work, cv_stream_t stream);
 
+/* ---- evaluation metric: the rank counts behind average precision and AUROC (losses.py:24-33, where auc calls
+ * sklearn's average_precision_score and roc_auc_score once per class on host copies of the softmax) ----
+ * score: [n][c] fp32 with row stride lds >= c; label: [n] with values in [0, c); order: [n] sample indices sorted by
+ * label (stable); start: [c + 1], class k owns order[start[k] .. start[k+1]).  For class k, with s_j = score[j][k],
+ * P positives (label == k) and N = n - P negatives, every positive i gets ge_pos_i = #{j positive : s_j >= s_i}
+ * (itself included), ge_neg_i = #{j negative : s_j >= s_i} and gt_neg_i = #{j negative : s_j > s_i}; 0.0 and -0.0
+ * are equal.  counts_out [n][3] (or NULL) receives (ge_pos, ge_neg, gt_neg) of every sample for its own class,
+ * ap_sum_out [c] = sum_i ge_pos_i / (ge_pos_i + ge_neg_i) in fp64 (AP_k = ap_sum / P), added in a fixed order: the
+ * result is bit-reproducible; u2_out [c] = sum_i [2 (N - ge_neg_i) + (ge_neg_i - gt_neg_i)], an exact integer
+ * (AUROC_k = u2 / (2 P N): Mann-Whitney with ties counted one half).  A class without positives gets 0 in both.
+ * The scores must be finite and the labels in range: the caller checks that, the kernel does not.  The grid is
+ * sized from n and c alone (no host read of the class sizes).  1 <= n <= 2^22, 1 <= c <= 2^22;
+ * work: cv_rank_auc_workspace_bytes(n, c) bytes (0 for sizes outside those limits), need not be zeroed. */
+size_t cv_rank_auc_workspace_bytes(int n, int c);
+int cv_rank_auc(const float* score, int lds, int n, int c, const int32_t* label, const int32_t* order,
+                const int32_t* start, uint32_t* counts_out, double* ap_sum_out, unsigned long long* u2_out, void* work,
+                cv_stream_t stream);
+
 /* ---- downstream probe (run_styledmnist_downstream_expr.py:110-117, trainer.py:125-131): the reference's `mlp` =
  * Linear(d,h) -> BatchNorm1d(h) -> ReLU -> Linear(h,c) on mu_c of the frozen VAE, nn.CrossEntropyLoss() defaults ----
  * Linear weights [out][in]; running statistics are the module's own buffers (updated in place by a training step:
