@@ -21,8 +21,11 @@
 //   mean_j (y_jd - mu_id)^2 = (Sy2_d - 2 mu_id Sy_d + N mu_id^2) / N
 // comes from the column moments the perm kernel leaves for L1OutUB, so it is O(N d) as well; dCLUB/dy needs the
 // E_d = sum_i 1/v_id, M_d = sum_i mu_id/v_id the rows kernel folds.  VarUB (mi_estimator.py:222-224) is the mean
-// over the N*dy elements of (mu^2 + e^lv - 1 - lv)/2 and does not depend on y.
-#include "cv_common.hpp"
+// over the N*dy elements of (mu^2 + e^lv - 1 - lv)/2 and does not depend on y.  CLUBMean (mi_estimator.py:65-105)
+// is CLUB with logvar == 0 and no p_logvar network: its cv_mlp carries NULL w3 / b3 / w4 / b4, the kernels stage a zero
+// p_logvar network for it (tanh(0) = 0, e^0 = 1 exactly) and run CLUB's code; its learning loss -mean_i sum_d
+// -(mu - y)^2 (mi_estimator.py:99-105, no division by two) is the shared one at logvar == 0.
+#include "cv_mi.hpp"
 
 namespace cv {
 
@@ -47,6 +50,7 @@ __device__ __forceinline__ void stage_mlp(const cv_mlp& P, MlpLds<DM>& L) {
   constexpr int PW = MlpLds<DM>::PW;
   const int t = threadIdx.x, nt = blockDim.x;
   const int dx = P.dx, h = P.h, dy = P.dy;
+  const bool lvnet = P.w3 != nullptr;  // (CLUBMean has no p_logvar: zero weights give logvar == tanh(0) == 0)
   // SU elements of each matrix per thread in flight per round trip, the four matrices' loads issued
   // together (a load -> LDS store per element made the staging one dependent round trip per element)
   constexpr int SU = 4;
@@ -58,9 +62,9 @@ __device__ __forceinline__ void stage_mlp(const cv_mlp& P, MlpLds<DM>& L) {
     for (int q = 0; q < SU; ++q) {
       const int i = i0 + q * nt;
       a1[q] = i < n13 ? P.w1[i] : 0.f;
-      a3[q] = i < n13 ? P.w3[i] : 0.f;
+      a3[q] = (lvnet && i < n13) ? P.w3[i] : 0.f;
       a2[q] = i < n24 ? P.w2[i] : 0.f;
-      a4[q] = i < n24 ? P.w4[i] : 0.f;
+      a4[q] = (lvnet && i < n24) ? P.w4[i] : 0.f;
     }
 #pragma unroll
     for (int q = 0; q < SU; ++q) {
@@ -79,9 +83,9 @@ __device__ __forceinline__ void stage_mlp(const cv_mlp& P, MlpLds<DM>& L) {
   }
   for (int i = t; i < 64; i += nt) {
     L.b1[i] = (i < h) ? P.b1[i] : 0.f;
-    L.b3[i] = (i < h) ? P.b3[i] : 0.f;
+    L.b3[i] = (lvnet && i < h) ? P.b3[i] : 0.f;
     L.b2[i] = (i < dy) ? P.b2[i] : 0.f;
-    L.b4[i] = (i < dy) ? P.b4[i] : 0.f;
+    L.b4[i] = (lvnet && i < dy) ? P.b4[i] : 0.f;
   }
   __syncthreads();
 }
@@ -155,46 +159,6 @@ __device__ __forceinline__ float mlp_bwd_row(const MlpLds<DM>& L, int dx, int h,
     }
   }
   return (lane < dx) ? dxv : 0.f;
-}
-
-// ---------------------------------------------------------------- workspace
-constexpr int MI_MAXN = 4096;      // largest batch of the one-workgroup device permutation (bitonic sort in LDS)
-constexpr int MI_MAXBIG = 1 << 20;  // largest batch at all (above MI_MAXN: mi_perm_big_kernel)
-#ifndef CV_MI_NB
-#define CV_MI_NB 64  // (64 row workgroups for the learning step measured +0.2 % on C3 over 32)
-#endif
-constexpr int MI_NB = CV_MI_NB;            // max row workgroups whose partials are folded
-constexpr int MI_FP = 2 + 128;             // per-workgroup forward partial: acc0, acc1, E[64], M[64]
-constexpr int MI_GSZ = 4 * 64 * 64 + 256;  // per-workgroup learning-gradient partial (lane-major)
-struct MiWork {
-  double* sums;       // Sy[64], Sy2[64], E[64], M[64]
-  double* fpart;      // [MI_NB][MI_FP]
-  double* lpart;      // [MI_NB]
-  unsigned* ticket;   // [0] rows arrivals, [1] learn-reduce arrivals (self-resetting)
-  float* gpart;       // [MI_NB][MI_GSZ]
-  int* perm;
-  int* invperm;
-};
-static inline size_t mi_work_bytes(int n) {
-  return 4 * 64 * 8 + MI_NB * MI_FP * 8 + MI_NB * 8 + 64 + (size_t)MI_NB * MI_GSZ * 4 + (size_t)2 * n * 4 + 64;
-}
-__host__ __device__ inline MiWork mi_work(void* base, int n) {
-  MiWork w;
-  char* p = (char*)base;
-  w.sums = (double*)p;
-  p += 4 * 64 * 8;
-  w.fpart = (double*)p;
-  p += MI_NB * MI_FP * 8;
-  w.lpart = (double*)p;
-  p += MI_NB * 8;
-  w.ticket = (unsigned*)p;
-  p += 64;
-  w.gpart = (float*)p;
-  p += (size_t)MI_NB * MI_GSZ * 4;
-  w.perm = (int*)p;
-  p += (size_t)n * 4;
-  w.invperm = (int*)p;
-  return w;
 }
 
 struct MiArgs {
@@ -561,41 +525,29 @@ __global__ __launch_bounds__(256) void mi_grad_kernel(const MiArgs A) {
         const float gm = bcast(dmu, k), gl = bcast(dlvp, k);
         if (lane < h) {
           atomicAdd(A.G.w2 + k * h + lane, gm * h1);
-          atomicAdd(A.G.w4 + k * h + lane, gl * h3);
+          if (A.G.w4) atomicAdd(A.G.w4 + k * h + lane, gl * h3);
         }
       }
       if (lane < dy) {
         atomicAdd(A.G.b2 + lane, dmu);
-        atomicAdd(A.G.b4 + lane, dlvp);
+        if (A.G.b4) atomicAdd(A.G.b4 + lane, dlvp);
       }
       for (int k = 0; k < dx; ++k) {
         const float xk = bcast(f.xv, k);
         if (lane < h) {
           atomicAdd(A.G.w1 + lane * dx + k, da1 * xk);
-          atomicAdd(A.G.w3 + lane * dx + k, da3 * xk);
+          if (A.G.w3) atomicAdd(A.G.w3 + lane * dx + k, da3 * xk);
         }
       }
       if (lane < h) {
         atomicAdd(A.G.b1 + lane, da1);
-        atomicAdd(A.G.b3 + lane, da3);
+        if (A.G.b3) atomicAdd(A.G.b3 + lane, da3);
       }
     }
   }
 }
 
 // ---------------------------------------------------------------- learning step
-struct LearnArgs {
-  cv_mlp P;
-  const float* x; int ldx;
-  const float* y; int ldy;
-  int n;
-  void* work;
-  float* loss_out;
-  // Adam (optional): flat arena
-  float* params; const float* grads; float* m; float* v; long numel;
-  const float* hyper; int64_t* step;
-};
-
 // per-workgroup partial, lane-major with pitch 64: [dW1: k*64+u][dW3][dW2: k*64+u][dW4] (DM*64 each),
 // then db1[64] db3[64] db2[64] db4[64]
 template <int DM>
@@ -676,13 +628,6 @@ __global__ __launch_bounds__(256) void mi_learn_rows_kernel(const LearnArgs A) {
   for (int i = t; i < (4 * DM * 64 + 256) / 4; i += 256) dst[i] = src[i];
   if (t == 0) W.lpart[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
-
-// parameter segments of the estimator: canonical element j of segment s is partial word
-// poff + (trans ? (j % inner)*64 + j / inner : (j / inner)*64 + j % inner)  (inner == 0: poff + j)
-struct LearnSegs {
-  float* g[8];
-  int len[8], inner[8], poff[8], trans[8];
-};
 
 // one thread per estimator parameter (or per arena word with Adam): fold the workgroup partials in
 // block order, write the gradient and take the Adam step on it
@@ -872,8 +817,15 @@ using namespace cv;
 
 extern "C" size_t cv_mi_workspace_bytes(int n) { return mi_work_bytes(n); }
 
-static int check_mlp(const cv_mlp* P) {
-  CV_REQUIRE(P && P->w1 && P->b1 && P->w2 && P->b2 && P->w3 && P->b3 && P->w4 && P->b4, "mi: MLP weights missing");
+// mean_only (CV_MI_CLUBMEAN, mi_estimator.py:65-105): no p_logvar network, its four pointers must be NULL
+static int check_mlp(const cv_mlp* P, bool mean_only) {
+  CV_REQUIRE(P && P->w1 && P->b1 && P->w2 && P->b2, "mi: MLP weights missing");
+  if (mean_only)  // (kind 5 names an estimator only together with its network shape)
+    CV_REQUIRE(!P->w3 && !P->b3 && !P->w4 && !P->b4,
+               "mi: unknown estimator %d for an MLP with p_logvar weights (CV_MI_CLUBMEAN: w3, b3, w4, b4 NULL)",
+               CV_MI_CLUBMEAN);
+  else
+    CV_REQUIRE(P->w3 && P->b3 && P->w4 && P->b4, "mi: MLP weights missing");
   CV_REQUIRE(P->dx > 0 && P->dx <= 64 && P->h > 0 && P->h <= 64 && P->dy > 0 && P->dy <= 64,
              "mi: MLP widths must be in 1..64 (dx=%d h=%d dy=%d)", P->dx, P->h, P->dy);
   return 0;
@@ -895,8 +847,11 @@ static int mlp_dm(const cv_mlp* P) {
   } while (0)
 
 static bool known_kind(int kind) {
-  return kind == CV_MI_CLUBSAMPLE || kind == CV_MI_L1OUT || kind == CV_MI_CLUB || kind == CV_MI_VARUB;
+  return kind == CV_MI_CLUBSAMPLE || kind == CV_MI_L1OUT || kind == CV_MI_CLUB || kind == CV_MI_VARUB ||
+         kind == CV_MI_CLUBMEAN;
 }
+// CLUBMean is CLUB evaluated with logvar == 0 (the kernels stage a zero p_logvar network for it)
+static int kernel_kind(int kind) { return kind == CV_MI_CLUBMEAN ? CV_MI_CLUB : kind; }
 
 static int mi_row_blocks(int n) {
   const int b = cdiv(n, 4);
@@ -907,13 +862,13 @@ extern "C" int cv_mi_forward(int kind, const cv_mlp* mlp, const float* x, int ld
                              const int64_t* perm, uint64_t seed, uint64_t* offset, void* work, float* mi_out,
                              cv_stream_t stream) {
   clear_error();
-  if (check_mlp(mlp)) return 1;
   CV_REQUIRE(known_kind(kind), "mi: unknown estimator %d", kind);
+  if (check_mlp(mlp, kind == CV_MI_CLUBMEAN)) return 1;
   CV_REQUIRE(x && y && work && n > 1 && n <= MI_MAXBIG, "mi_forward: bad args (2 <= n <= %d)", MI_MAXBIG);
   CV_REQUIRE(kind != CV_MI_CLUBSAMPLE || perm || offset, "mi_forward: CLUBSample needs perm or an RNG offset");
   MiArgs a;
   memset(&a, 0, sizeof(a));
-  a.kind = kind;
+  a.kind = kernel_kind(kind);
   a.P = *mlp;
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.n = n;
   a.perm_in = perm; a.seed = seed; a.offset = perm ? nullptr : offset;
@@ -935,13 +890,13 @@ extern "C" int cv_mi_backward(int kind, const cv_mlp* mlp, const float* x, int l
                               int accumulate, const cv_mlp_grad* g, const float* heads, const float* z,
                               float* dheads, int d, cv_stream_t stream) {
   clear_error();
-  if (check_mlp(mlp)) return 1;
   CV_REQUIRE(known_kind(kind), "mi: unknown estimator %d", kind);
+  if (check_mlp(mlp, kind == CV_MI_CLUBMEAN)) return 1;
   CV_REQUIRE(x && y && work && n > 1 && n <= MI_MAXBIG, "mi_backward: bad args");
   CV_REQUIRE(!dheads || (heads && z && d == mlp->dx && d == mlp->dy), "mi_backward: chain mode needs heads, z, d");
   MiArgs a;
   memset(&a, 0, sizeof(a));
-  a.kind = kind;
+  a.kind = kernel_kind(kind);
   a.P = *mlp;
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.n = n;
   a.work = work;
@@ -961,17 +916,21 @@ extern "C" int cv_mi_learning_step(const cv_mlp* mlp, const float* x, int ldx, c
                                    const float* grads, float* exp_avg, float* exp_avg_sq, int64_t numel,
                                    const float* hyper, int64_t* step, cv_stream_t stream) {
   clear_error();
-  if (check_mlp(mlp)) return 1;
-  CV_REQUIRE(x && y && work && g && g->w1 && g->b1 && g->w2 && g->b2 && g->w3 && g->b3 && g->w4 && g->b4 && n > 0,
-             "mi_learning_step: bad args");
+  // (no kind argument: a cv_mlp without p_logvar pointers is CLUBMean's, mi_estimator.py:99-105)
+  const bool mean_only = mlp && !mlp->w3 && !mlp->b3 && !mlp->w4 && !mlp->b4;
+  if (check_mlp(mlp, mean_only)) return 1;
+  CV_REQUIRE(x && y && work && g && g->w1 && g->b1 && g->w2 && g->b2 && n > 0, "mi_learning_step: bad args");
+  CV_REQUIRE(mean_only ? (!g->w3 && !g->b3 && !g->w4 && !g->b4) : (g->w3 && g->b3 && g->w4 && g->b4),
+             "mi_learning_step: bad args (the p_logvar gradients follow the p_logvar weights)");
   CV_REQUIRE(!params || (grads && exp_avg && exp_avg_sq && hyper && step && numel > 0),
              "mi_learning_step: Adam arena incomplete");
   const int dx = mlp->dx, h = mlp->h, dy = mlp->dy;
   float* const gp[8] = {g->w1, g->w3, g->w2, g->w4, g->b1, g->b3, g->b2, g->b4};
-  const int ln[8] = {h * dx, h * dx, dy * h, dy * h, h, h, dy, dy};
+  const int lq = mean_only ? 0 : 1;  // (CLUBMean: the p_logvar segments are empty)
+  const int ln[8] = {h * dx, lq * h * dx, dy * h, lq * dy * h, h, lq * h, dy, lq * dy};
   if (params)
     for (int s = 0; s < 8; ++s)
-      CV_REQUIRE(gp[s] >= grads && gp[s] + ln[s] <= grads + numel,
+      CV_REQUIRE(ln[s] == 0 || (gp[s] >= grads && gp[s] + ln[s] <= grads + numel),
                  "mi_learning_step: with Adam the gradients must live in the grads arena");
   LearnArgs a;
   memset(&a, 0, sizeof(a));
@@ -995,10 +954,14 @@ extern "C" int cv_mi_learning_step(const cv_mlp* mlp, const float* x, int ldx, c
     sg.g[s] = gp[s]; sg.len[s] = ln[s]; sg.inner[s] = in[s]; sg.poff[s] = po[s]; sg.trans[s] = tr[s];
     total += ln[s];
   }
-  const long dom = params ? (long)numel : (long)total;
+  return mi_learn_reduce_launch(a, sg, nb, total, S(stream));
+}
+
+int cv::mi_learn_reduce_launch(const LearnArgs& a, const LearnSegs& sg, int nb, int total, hipStream_t st) {
+  const long dom = a.params ? a.numel : (long)total;
   int blocks = cdiv(dom, 256);
   if (blocks > 256) blocks = 256;
-  hipLaunchKernelGGL(mi_learn_reduce_kernel, dim3(blocks), dim3(256), 0, S(stream), a, sg, nb, total);
+  hipLaunchKernelGGL(mi_learn_reduce_kernel, dim3(blocks), dim3(256), 0, st, a, sg, nb, total);
   CV_LAUNCH_CHECK("mi_learning_step.reduce");
   return 0;
 }

@@ -31,7 +31,7 @@ def stat_repl(C: int) -> int:
 XF_NONE, XF_BNRELU, XF_BNBWD = 0, 1, 2
 STAT_NONE, STAT_FWD, STAT_BWD = 0, 1, 2
 SIM = {"cosine": 0, "l2": 1, "modified_l2": 2, "jeffrey": 3, "mahalanobis": 4}
-MI_NONE, MI_CLUBSAMPLE, MI_L1OUT, MI_CLUB, MI_VARUB = 0, 1, 2, 3, 4  # CV_MI_*
+MI_NONE, MI_CLUBSAMPLE, MI_L1OUT, MI_CLUB, MI_VARUB, MI_CLUBMEAN, MI_INFONCE = 0, 1, 2, 3, 4, 5, 6  # CV_MI_*
 MMA_FP32, MMA_BF16 = 0, 1  # CV_MMA_*
 GROUP = {"MLVAE": 0, "GVAE": 1}  # CV_GROUP_*
 PRECISION = {"fp32": MMA_FP32, "bf16": MMA_BF16}
@@ -145,6 +145,18 @@ class cv_mlp(ctypes.Structure):
 
 class cv_mlp_grad(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4")]
+
+
+class cv_critic(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("w1", "b1", "w2", "b2")] + [
+        ("dx", c_int),
+        ("dy", c_int),
+        ("h", c_int),
+    ]
+
+
+class cv_critic_grad(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("w1", "b1", "w2", "b2")]
 
 
 class cv_probe(ctypes.Structure):
@@ -400,6 +412,22 @@ _SIGS = {
     "cv_mi_learning_step": (
         c_int,
         [_P(cv_mlp), c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, _P(cv_mlp_grad), c_void_p,
+         c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    ),
+    "cv_infonce_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "cv_infonce_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "cv_infonce_forward": (
+        c_int,
+        [_P(cv_critic), c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    ),
+    "cv_infonce_backward": (
+        c_int,
+        [_P(cv_critic), c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,
+         c_void_p, c_int, c_int, _P(cv_critic_grad), c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    ),
+    "cv_infonce_learning_step": (
+        c_int,
+        [_P(cv_critic), c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, _P(cv_critic_grad), c_void_p,
          c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     ),
     "cv_knn_mi_workspace_bytes": (c_size_t, [c_int, c_int]),

@@ -13,7 +13,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib, rng
-from ._lib import GROUP, MI_CLUBSAMPLE, SIM, cv_mlp, cv_mlp_grad, cv_ntxent_branch
+from ._lib import GROUP, MI_CLUBSAMPLE, SIM, cv_critic, cv_critic_grad, cv_mlp, cv_mlp_grad, cv_ntxent_branch
 from .plan import Program, Workspace, ensure_arena, pack_program
 
 
@@ -355,22 +355,59 @@ class ContrastiveFn(torch.autograd.Function):
 # ----------------------------------------------------------------------------- MI estimators
 
 
-def mlp_struct(est) -> cv_mlp:
-    """cv_mlp over an estimator's p_mu / p_logvar Sequentials (mi_estimator.py:111-122)."""
-    l1, l2 = est.p_mu[0], est.p_mu[2]
-    l3, l4 = est.p_logvar[0], est.p_logvar[2]
-    for t in (l1.weight, l2.weight, l3.weight, l4.weight):
+def _est_family(est) -> str:
+    """'critic' (InfoNCE: F_func), 'mean' (CLUBMean: p_mu only) or 'q' (p_mu and p_logvar)."""
+    if hasattr(est, "F_func"):
+        return "critic"
+    return "q" if hasattr(est, "p_logvar") else "mean"
+
+
+def _check_weights(ts):
+    for t in ts:
         if not t.is_contiguous() or t.dtype != torch.float32:
             raise RuntimeError("estimator weights must be contiguous fp32")
+
+
+def mlp_struct(est) -> cv_mlp:
+    """cv_mlp over an estimator's p_mu / p_logvar Sequentials (mi_estimator.py:111-122); CLUBMean
+    (mi_estimator.py:99-105) has no p_logvar: its four pointers are NULL."""
+    l1, l2 = est.p_mu[0], est.p_mu[2]
+    if _est_family(est) == "mean":
+        _check_weights((l1.weight, l2.weight))
+        return cv_mlp(l1.weight.data_ptr(), l1.bias.data_ptr(), l2.weight.data_ptr(), l2.bias.data_ptr(),
+                      None, None, None, None, l1.in_features, l1.out_features, l2.out_features)
+    l3, l4 = est.p_logvar[0], est.p_logvar[2]
+    _check_weights((l1.weight, l2.weight, l3.weight, l4.weight))
     return cv_mlp(l1.weight.data_ptr(), l1.bias.data_ptr(), l2.weight.data_ptr(), l2.bias.data_ptr(),
                   l3.weight.data_ptr(), l3.bias.data_ptr(), l4.weight.data_ptr(), l4.bias.data_ptr(),
                   l1.in_features, l1.out_features, l2.out_features)
 
 
+def critic_struct(est, dx: int) -> cv_critic:
+    """cv_critic over InfoNCE.F_func (mi_estimator.py:250-253); dx = the width of x_samples (F_func's first Linear
+    takes [x, y])."""
+    l1, l2 = est.F_func[0], est.F_func[2]
+    _check_weights((l1.weight, l2.weight))
+    return cv_critic(l1.weight.data_ptr(), l1.bias.data_ptr(), l2.weight.data_ptr(), l2.bias.data_ptr(),
+                     dx, l1.in_features - dx, l1.out_features)
+
+
 def est_params(est):
+    fam = _est_family(est)
+    if fam == "critic":
+        l1, l2 = est.F_func[0], est.F_func[2]
+        return [l1.weight, l1.bias, l2.weight, l2.bias]
     l1, l2 = est.p_mu[0], est.p_mu[2]
+    if fam == "mean":
+        return [l1.weight, l1.bias, l2.weight, l2.bias]
     l3, l4 = est.p_logvar[0], est.p_logvar[2]
     return [l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias, l4.weight, l4.bias]
+
+
+def mlp_grad_struct(est, ptrs) -> cv_mlp_grad:
+    """cv_mlp_grad over est_params-ordered pointers (CLUBMean: the p_logvar half NULL)."""
+    ptrs = list(ptrs)
+    return cv_mlp_grad(*(ptrs + [None] * (8 - len(ptrs))))
 
 
 class MIUpperBoundFn(torch.autograd.Function):
@@ -407,7 +444,7 @@ class MIUpperBoundFn(torch.autograd.Function):
         dy = torch.empty_like(yy)
         params = est_params(ctx.est)
         gb = [torch.zeros_like(p) for p in params]
-        G = cv_mlp_grad(*[t.data_ptr() for t in gb])
+        G = mlp_grad_struct(ctx.est, [t.data_ptr() for t in gb])
         _lib.call("cv_mi_backward", ctx.kind, ctx.mlp, xx.data_ptr(), xx.stride(0), yy.data_ptr(), yy.stride(0), n,
                   work.data_ptr(), gg.data_ptr(), 1.0, dx.data_ptr(), dy.data_ptr(), dxw, 0, G, None, None, None,
                   0, _lib.stream_handle())
@@ -424,7 +461,7 @@ class LearningLossFn(torch.autograd.Function):
         mlp = mlp_struct(est)
         ps = est_params(est)
         gb = [torch.empty_like(p) for p in ps]
-        G = cv_mlp_grad(*[t.data_ptr() for t in gb])
+        G = mlp_grad_struct(est, [t.data_ptr() for t in gb])
         out = torch.empty((), dtype=torch.float32, device=xx.device)
         work = torch.zeros(int(_lib.lib().cv_mi_workspace_bytes(n)) // 4 + 16, dtype=torch.float32,
                            device=xx.device)
@@ -440,3 +477,67 @@ class LearningLossFn(torch.autograd.Function):
             raise NotImplementedError("learning_loss gradients w.r.t. its inputs (the reference detaches z)")
         gs = [t * g for t in ctx.gb]
         return (None, None, None, *gs)
+
+
+def _nce_work(n, h, device):
+    return torch.zeros(int(_lib.lib().cv_infonce_workspace_bytes(n, h)) // 4 + 16, dtype=torch.float32, device=device)
+
+
+class InfoNCEFn(torch.autograd.Function):
+    """InfoNCE.forward (mi_estimator.py:259-270) in O(N h) memory."""
+
+    @staticmethod
+    def forward(ctx, x, y, est, *params):
+        xx, yy = _f32c(x), _f32c(y)
+        n = xx.shape[0]
+        cr = critic_struct(est, xx.shape[1])
+        work = _nce_work(n, cr.h, xx.device)
+        out = torch.empty((), dtype=torch.float32, device=xx.device)
+        _lib.call("cv_infonce_forward", cr, xx.data_ptr(), xx.stride(0), yy.data_ptr(), yy.stride(0), n,
+                  work.data_ptr(), out.data_ptr(), _lib.stream_handle())
+        ctx.save_for_backward(xx, yy, work)
+        ctx.est, ctx.cr = est, cr
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xx, yy, work = ctx.saved_tensors
+        n = xx.shape[0]
+        gg = _f32c(g.reshape(1))
+        dx = torch.empty_like(xx)
+        dy = torch.empty_like(yy)
+        if dx.shape[1] != dy.shape[1]:  # (one leading dimension for both: a shared buffer)
+            buf = torch.empty(n, max(dx.shape[1], dy.shape[1]) * 2, dtype=torch.float32, device=xx.device)
+            dx, dy = buf[:, :dx.shape[1]], buf[:, buf.shape[1] // 2:buf.shape[1] // 2 + dy.shape[1]]
+        gb = [torch.empty_like(p) for p in est_params(ctx.est)]
+        G = cv_critic_grad(*[t.data_ptr() for t in gb])
+        _lib.call("cv_infonce_backward", ctx.cr, xx.data_ptr(), xx.stride(0), yy.data_ptr(), yy.stride(0), n,
+                  work.data_ptr(), gg.data_ptr(), 1.0, dx.data_ptr(), dy.data_ptr(), dx.stride(0), 0, G, None, None,
+                  None, 0, _lib.stream_handle())
+        return (dx, dy, None, *gb)
+
+
+class InfoNCELearningLossFn(torch.autograd.Function):
+    """InfoNCE.learning_loss = -forward (mi_estimator.py:272-273); gradients for the critic only (the reference
+    detaches z)."""
+
+    @staticmethod
+    def forward(ctx, x, y, est, *params):
+        xx, yy = _f32c(x), _f32c(y)
+        n = xx.shape[0]
+        cr = critic_struct(est, xx.shape[1])
+        gb = [torch.empty_like(p) for p in est_params(est)]
+        G = cv_critic_grad(*[t.data_ptr() for t in gb])
+        out = torch.empty((), dtype=torch.float32, device=xx.device)
+        work = _nce_work(n, cr.h, xx.device)
+        _lib.call("cv_infonce_learning_step", cr, xx.data_ptr(), xx.stride(0), yy.data_ptr(), yy.stride(0), n,
+                  work.data_ptr(), out.data_ptr(), G, None, None, None, None, 0, None, None, _lib.stream_handle())
+        ctx.gb = gb
+        ctx.xy_grad = (x.requires_grad, y.requires_grad)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if any(ctx.xy_grad):
+            raise NotImplementedError("learning_loss gradients w.r.t. its inputs (the reference detaches z)")
+        return (None, None, None, *[t * g for t in ctx.gb])

@@ -36,6 +36,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import warnings
 from dataclasses import dataclass
 
 import torch
@@ -43,15 +44,31 @@ import torch.distributed as dist
 
 from . import _lib, rng
 from . import dist as cvdist
-from ._lib import (GROUP, MI_CLUB, MI_CLUBSAMPLE, MI_L1OUT, MI_VARUB, SIM, cv_latent_chain, cv_mlp, cv_mlp_grad,
-                   cv_ntxent_branch, cv_tc_disc, cv_tc_grad)
-from .autograd import est_params, mlp_struct
+from ._lib import (GROUP, MI_CLUB, MI_CLUBMEAN, MI_CLUBSAMPLE, MI_INFONCE, MI_L1OUT, MI_VARUB, SIM, cv_critic_grad,
+                   cv_latent_chain, cv_mlp, cv_ntxent_branch, cv_tc_disc, cv_tc_grad)
+from .autograd import critic_struct, est_params, mlp_grad_struct, mlp_struct
 from ._lib import cv_conv_pack
 from .plan import (DeferGroup, ParamArena, Program, Workspace, ensure_arena, pack_program, ptr_array,
                    struct_array)
 
 # the estimator classes of src.models.mi_estimator the fused CLEAR-MIM step carries, and their CV_MI_* kind
-MI_KINDS = {"CLUBSample": MI_CLUBSAMPLE, "L1OutUB": MI_L1OUT, "CLUB": MI_CLUB, "VarUB": MI_VARUB}
+# (CLUBMean and InfoNCE only when built with backend="device" and inside the device envelope: ClearStep.build)
+MI_KINDS = {"CLUBSample": MI_CLUBSAMPLE, "L1OutUB": MI_L1OUT, "CLUB": MI_CLUB, "VarUB": MI_VARUB,
+            "CLUBMean": MI_CLUBMEAN, "InfoNCE": MI_INFONCE}
+
+
+def _opt_in_estimator_ok(est, d: int) -> bool:
+    """CLUBMean / InfoNCE join the fused step when they were built with backend="device", take the VAE's two latent
+    halves (x_dim = y_dim = d) within the kernels' widths, and the step is a single-process one (the data-parallel
+    programs are not covered for these two: they train on the module path there)."""
+    if getattr(est, "backend", None) != "device":
+        return False
+    if _dist_world() > 1 or (os.environ.get("CVHIP_FORCE_DP", "0") == "1" and dist.is_available()
+                             and dist.is_initialized()):
+        return False
+    if hasattr(est, "F_func"):
+        return est.F_func[0].in_features == 2 * d and est.device_supported(2, d)
+    return (est.device_supported() and est.p_mu[0].in_features == d and est.p_mu[2].out_features == d)
 
 
 # CVHIP_GRAPH_COLLECTIVES=1 (opt-in): a data-parallel step is captured as ONE graph with its RCCL all-reduces inside
@@ -292,10 +309,18 @@ class ClearStep:
         elif trainer.sim_fn not in SIM:
             raise ValueError("unimplemented similarity measure.")
         if mode == "mim":
-            from src.models.mi_estimator import CLUB, CLUBSample, L1OutUB, VarUB
+            from src.models.mi_estimator import CLUB, CLUBMean, CLUBSample, InfoNCE, L1OutUB, VarUB
 
             est = trainer.mi_estimator
-            if type(est) not in (CLUBSample, L1OutUB, CLUB, VarUB):
+            if type(est) in (CLUBMean, InfoNCE):
+                if not _opt_in_estimator_ok(est, vae._cv_spec.d):
+                    if getattr(est, "backend", None) == "device" and not getattr(est, "_cv_step_warned", False):
+                        est._cv_step_warned = True
+                        warnings.warn(f"{type(est).__name__}(backend='device') is outside the fused step's envelope "
+                                      "(latent halves <= 64 wide, hidden_size <= 64, single process); training on "
+                                      "the module path", RuntimeWarning, stacklevel=2)
+                    return None
+            elif type(est) not in (CLUBSample, L1OutUB, CLUB, VarUB):
                 return None
             if not _AdamState.supported(trainer.mi_estimator_optimizer, est_params(est)):
                 return None
@@ -465,6 +490,9 @@ class ClearStep:
         if self.mode == "tc":
             ctx.tc_work = torch.zeros(int(_lib.lib().cv_tc_workspace_bytes(2 * d)) // 4 + 4, dtype=torch.float32,
                                       device=dev)
+        if self.mode == "mim" and self.kind == MI_INFONCE:  # the InfoNCE workspace, beside ws.mi_work
+            ws.nce_work = torch.zeros(int(_lib.lib().cv_infonce_workspace_bytes(n, self.est.F_func[0].out_features))
+                                      // 4 + 16, dtype=torch.float32, device=dev)
         if self.mode == "mim" and not self.dp and MIM_BRANCHES > 0:
             # the branched estimator forwards: own activations and statistics per update, one in-launch split-K
             # workspace per decoder lane
@@ -574,7 +602,15 @@ class ClearStep:
                     ctypes.c_float(float(hp["temperature"])))
         lat_inj = Program()
         lat_inj.extend(lat)
-        if self.mode == "mim":
+        if self.mode == "mim" and self.kind == MI_INFONCE:
+            cr = critic_struct(self.est, d)
+            zp = ws.z.data_ptr()
+            for prog in (lat, lat_inj):
+                prog.add("cv_infonce_forward", cr, zp, 2 * d, zp + 4 * d, 2 * d, n, ws.nce_work,
+                         ws.losses.data_ptr() + 20)
+                prog.add("cv_infonce_backward", cr, zp, 2 * d, zp + 4 * d, 2 * d, n, ws.nce_work, None,
+                         ctypes.c_float(float(hp["lambda"])), None, None, 0, 1, None, ws.heads, ws.z, ws.dheads, d)
+        elif self.mode == "mim":
             mlp = mlp_struct(self.est)
             zp = ws.z.data_ptr()
             for prog, pin in ((lat, None), (lat_inj, ctx.perm_buf)):
@@ -665,10 +701,15 @@ class ClearStep:
         in the same launch."""
         ws, d, E = ctx.ws, self.spec.d, self.est_arena
         zp = z.data_ptr()
-        G = cv_mlp_grad(*[E.gptr(p) for p in est_params(self.est)])
+        adam_args = self.est_adam.args() if adam else (None, None, None, None, 0, None, None)
+        if self.kind == MI_INFONCE:
+            G = cv_critic_grad(*[E.gptr(p) for p in est_params(self.est)])
+            prog.add("cv_infonce_learning_step", critic_struct(self.est, d), zp, 2 * d, zp + 4 * d, 2 * d, ws.n,
+                     ws.nce_work, self.learn.data_ptr() + 4 * j, G, *adam_args)
+            return
+        G = mlp_grad_struct(self.est, [E.gptr(p) for p in est_params(self.est)])
         prog.add("cv_mi_learning_step", mlp_struct(self.est), zp, 2 * d, zp + 4 * d, 2 * d, ws.n, ws.mi_work,
-                 self.learn.data_ptr() + 4 * j, G,
-                 *(self.est_adam.args() if adam else (None, None, None, None, 0, None, None)))
+                 self.learn.data_ptr() + 4 * j, G, *adam_args)
 
     def _mim_learn_forward(self, prog: Program, ctx: _StepCtx, j: int, inject: bool):
         """The part of estimator forward j before its decoder pass (sequential and data-parallel forms): the encoder

@@ -1,24 +1,30 @@
-"""MI upper-bound estimators with the reference's modules and method names
-(code/src/models/mi_estimator.py).  The four estimators over the q(y|x) network pair (p_mu, p_logvar) —
-CLUBSample and L1OutUB, which the CLEAR-MIM scripts instantiate, and CLUB and VarUB,
-which `get_clearmimvae_trainer(mi_estimator=...)` resolves as well — run on libclearvae_hip.so: forward /
-learning_loss / their gradients are HIP kernels (cvhip.autograd.MIUpperBoundFn / LearningLossFn), and
-ClearStep fuses all four.  CLUB and VarUB keep their plain-PyTorch forward on CPU tensors (they never
-raised there); CLUBSample and L1OutUB require the GPU.
+"""MI estimators with the reference's modules and method names (code/src/models/mi_estimator.py).  The four
+estimators over the q(y|x) network pair (p_mu, p_logvar) — CLUBSample and L1OutUB, which the CLEAR-MIM scripts
+instantiate, and CLUB and VarUB, which `get_clearmimvae_trainer(mi_estimator=...)` resolves as
+well — run on libclearvae_hip.so: forward / learning_loss / their gradients are HIP kernels
+(cvhip.autograd.MIUpperBoundFn / LearningLossFn), and ClearStep fuses all four.  CLUB and VarUB keep their
+plain-PyTorch forward on CPU tensors (they never raised there); CLUBSample and L1OutUB require the GPU.
 
-CLUBMean (a different network: no p_logvar) and InfoNCE (a lower bound with a critic network) are never
-instantiated by a CLEAR trainer, script or demo; they are kept importable as plain
-PyTorch tensor code.
+CLUBMean (a different network: no p_logvar) and InfoNCE (a lower bound with a critic network), the other two names
+the factory resolves, take a `backend` switch: "torch" (the default) is plain PyTorch tensor code; "device" runs
+CUDA tensors on libclearvae_hip.so (CLUBMean through the CLUB kernels with logvar == 0, InfoNCE through
+cv_infonce_* in O(N h) memory instead of the reference's [N, N, dx+dy] tiling) and lets ClearStep fuse them.  The
+device envelope is 2 <= n (InfoNCE: n <= 16384), x_dim, y_dim, hidden_size <= 64 and, for CLUBMean, a hidden layer;
+a call outside it warns once and runs the torch formulas.  `backend=None` reads CVHIP_MI_EST=torch|device.
 """
 
 from __future__ import annotations
+
+import os
+import warnings
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
 from cvhip import autograd as _ag
-from cvhip._lib import MI_CLUB, MI_CLUBSAMPLE, MI_L1OUT, MI_VARUB
+from cvhip import _lib
+from cvhip._lib import MI_CLUB, MI_CLUBMEAN, MI_CLUBSAMPLE, MI_L1OUT, MI_VARUB
 
 
 def _q_nets(x_dim, y_dim, hidden_size):
@@ -88,31 +94,78 @@ class VarUB(_QEstimator):
         return 1.0 / 2.0 * (mu**2 + logvar.exp() - 1.0 - logvar).mean()
 
 
-# ----------------------------------------------------------------------------- not on the hot path
+# ----------------------------------------------------------------------------- CLUBMean, InfoNCE (backend switch)
+
+MI_EST_BACKENDS = ("torch", "device")
+
+
+def resolve_backend(backend=None) -> str:
+    """"torch" or "device": the argument, else the environment variable CVHIP_MI_EST, else "torch"."""
+    if backend is None:
+        backend = os.environ.get("CVHIP_MI_EST") or "torch"
+    if backend not in MI_EST_BACKENDS:
+        raise ValueError(f"MI estimator backend must be one of {MI_EST_BACKENDS}, got {backend!r}")
+    return backend
+
+
+_warned = set()
+
+
+def _warn_once(key, msg):
+    if key not in _warned:
+        _warned.add(key)
+        warnings.warn(msg, RuntimeWarning, stacklevel=3)
 
 
 class CLUBMean(nn.Module):
-    def __init__(self, x_dim, y_dim, hidden_size=None):
+    """CLUB with logvar == 0 (mi_estimator.py:65-105).  backend="device": CUDA tensors run the CLUB kernels
+    (CV_MI_CLUBMEAN) when there is a hidden layer and x_dim, y_dim, hidden_size <= 64."""
+
+    def __init__(self, x_dim, y_dim, hidden_size=None, backend=None):
         super().__init__()
+        self.backend = resolve_backend(backend)
         if hidden_size is None:
             self.p_mu = nn.Linear(x_dim, y_dim)
         else:
             self.p_mu = nn.Sequential(nn.Linear(x_dim, int(hidden_size)), nn.ReLU(), nn.Linear(int(hidden_size), y_dim))
 
+    def device_supported(self, n=None) -> bool:
+        """The geometry the device path serves (any batch of at least 2 rows)."""
+        if not isinstance(self.p_mu, nn.Sequential):
+            return False
+        l1, l2 = self.p_mu[0], self.p_mu[2]
+        return (max(l1.in_features, l1.out_features, l2.out_features) <= 64 and l1.in_features == l2.out_features
+                and (n is None or n >= 2))
+
+    def _device(self, x_samples, y_samples) -> bool:
+        if self.backend != "device" or x_samples.device.type != "cuda":
+            return False
+        if self.device_supported(x_samples.shape[0]) and x_samples.dim() == 2:
+            return True
+        _warn_once(("CLUBMean", id(self)), "CLUBMean(backend='device'): outside the device envelope (a hidden layer, "
+                   "x_dim == y_dim <= 64, hidden_size <= 64, n >= 2); running the torch path")
+        return False
+
     def get_mu_logvar(self, x_samples):
         return self.p_mu(x_samples), 0
 
     def forward(self, x_samples, y_samples):
+        if self._device(x_samples, y_samples):
+            return _ag.MIUpperBoundFn.apply(x_samples, y_samples, self, MI_CLUBMEAN, *_ag.est_params(self))
         mu, _ = self.get_mu_logvar(x_samples)
         positive = -((mu - y_samples) ** 2) / 2.0
         negative = -((y_samples.unsqueeze(0) - mu.unsqueeze(1)) ** 2).mean(dim=1) / 2.0
         return (positive.sum(dim=-1) - negative.sum(dim=-1)).mean()
 
     def loglikeli(self, x_samples, y_samples):
+        if self._device(x_samples, y_samples):
+            return -self.learning_loss(x_samples, y_samples)
         mu, _ = self.get_mu_logvar(x_samples)
         return (-((mu - y_samples) ** 2)).sum(dim=1).mean(dim=0)
 
     def learning_loss(self, x_samples, y_samples):
+        if self._device(x_samples, y_samples):
+            return _ag.LearningLossFn.apply(x_samples, y_samples, self, *_ag.est_params(self))
         return -self.loglikeli(x_samples, y_samples)
 
 
@@ -125,13 +178,38 @@ def logsumexp(x: Tensor, dim: int) -> Tensor:
 
 
 class InfoNCE(nn.Module):
-    def __init__(self, x_dim, y_dim, hidden_size):
+    """InfoNCE lower bound (mi_estimator.py:245-273).  backend="device": CUDA tensors run cv_infonce_* (the critic's
+    first Linear factored into an x part and a y part, O(N h) memory) for 2 <= n <= 16384 and x_dim, y_dim,
+    hidden_size <= 64."""
+
+    def __init__(self, x_dim, y_dim, hidden_size, backend=None):
         super().__init__()
+        self.backend = resolve_backend(backend)
+        self.x_dim = int(x_dim)
         self.F_func = nn.Sequential(
             nn.Linear(x_dim + y_dim, hidden_size), nn.ReLU(), nn.Linear(hidden_size, 1), nn.Softplus()
         )
 
+    def device_supported(self, n=None, x_dim=None) -> bool:
+        l1 = self.F_func[0]
+        dx = self.x_dim if x_dim is None else int(x_dim)
+        return bool(_lib.lib().cv_infonce_supported(2 if n is None else int(n), dx, l1.in_features - dx,
+                                                    l1.out_features))
+
+    def _device(self, x_samples, y_samples) -> bool:
+        if self.backend != "device" or x_samples.device.type != "cuda":
+            return False
+        if (x_samples.dim() == 2 and y_samples.dim() == 2
+                and x_samples.shape[1] + y_samples.shape[1] == self.F_func[0].in_features
+                and self.device_supported(x_samples.shape[0], x_samples.shape[1])):
+            return True
+        _warn_once(("InfoNCE", id(self)), "InfoNCE(backend='device'): outside the device envelope (2 <= n <= 16384, "
+                   "x_dim, y_dim, hidden_size <= 64); running the torch path")
+        return False
+
     def forward(self, x_samples, y_samples):
+        if self._device(x_samples, y_samples):
+            return _ag.InfoNCEFn.apply(x_samples, y_samples, self, *_ag.est_params(self))
         n = y_samples.shape[0]
         x_tile = x_samples.unsqueeze(0).repeat((n, 1, 1))
         y_tile = y_samples.unsqueeze(1).repeat((1, n, 1))
@@ -140,4 +218,6 @@ class InfoNCE(nn.Module):
         return t0.mean() - (t1.logsumexp(dim=1).mean() - torch.tensor(n).log())
 
     def learning_loss(self, x_samples, y_samples):
+        if self._device(x_samples, y_samples):
+            return _ag.InfoNCELearningLossFn.apply(x_samples, y_samples, self, *_ag.est_params(self))
         return -self.forward(x_samples, y_samples)

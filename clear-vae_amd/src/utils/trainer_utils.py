@@ -92,11 +92,16 @@ def get_cleartcvae_trainer(beta, la, vae_lr, factor_cls_lr, z_dim, alpha, temper
 
 def get_clearmimvae_trainer(beta, mi_estimator: str, la, vae_lr, mi_estimator_lr, z_dim, alpha, temperature,
                             device, vae_arch: str = "VAE", in_channel: int = 1, verbose_period: int = 5,
-                            precision: str = "fp32"):
-    """(trainer_utils.py:160-201); `precision` as in get_clearvae_trainer."""
+                            precision: str = "fp32", backend=None):
+    """(trainer_utils.py:160-201); `precision` as in get_clearvae_trainer.  `backend` (not in the reference) goes to
+    the two estimators that take the switch, CLUBMean and InfoNCE: "torch" (their default) or "device" (HIP kernels,
+    fused into the one-graph step; src.models.mi_estimator); None reads CVHIP_MI_EST.  The other four names always
+    run on the device and ignore it."""
     vae = _resolve(vae_arch)(total_z_dim=z_dim, in_channel=in_channel).to(device)
     set_precision(vae, precision)
-    est = _resolve(mi_estimator)(x_dim=z_dim // 2, y_dim=z_dim // 2, hidden_size=z_dim).to(device)
+    est_cls = _resolve(mi_estimator)
+    est_kw = {"backend": backend} if est_cls in (CLUBMean, InfoNCE) else {}
+    est = est_cls(x_dim=z_dim // 2, y_dim=z_dim // 2, hidden_size=z_dim, **est_kw).to(device)
     vae_opt = torch.optim.Adam(vae.parameters(), lr=vae_lr)
     est_opt = torch.optim.Adam(est.parameters(), lr=mi_estimator_lr)
     return ClearMIMVAETrainer(

@@ -471,10 +471,17 @@ int cv_latent_step(const float* heads, const float* z, const float* dz, int n, i
                    const int64_t* label, int sim, float temperature, cv_stream_t stream);
 
 /* ---- MI upper bounds (mi_estimator.py:108-198; CLUB: mi_estimator.py:43-55, VarUB: mi_estimator.py:222-224) ---- */
-enum { CV_MI_NONE = 0, CV_MI_CLUBSAMPLE = 1, CV_MI_L1OUT = 2, CV_MI_CLUB = 3, CV_MI_VARUB = 4 };
+enum { CV_MI_NONE = 0, CV_MI_CLUBSAMPLE = 1, CV_MI_L1OUT = 2, CV_MI_CLUB = 3, CV_MI_VARUB = 4,
+       /* CLUBMean (mi_estimator.py:65-105): CLUB with logvar == 0 and no p_logvar network; served by the cv_mi_*
+        * entry points with a cv_mlp whose w3, b3, w4, b4 are NULL (and h = hidden_size, not hidden_size // 2) */
+       CV_MI_CLUBMEAN = 5,
+       /* InfoNCE (mi_estimator.py:245-273): a tag for callers that switch on the estimator; the cv_mi_* entry
+        * points reject it, its kernels are the cv_infonce_* entry points below */
+       CV_MI_INFONCE = 6 };
 
 /* q(y|x) MLPs (mi_estimator.py:111-122): p_mu = L(dx,h)-ReLU-L(h,dy);
- * p_logvar = L(dx,h)-ReLU-L(h,dy)-Tanh; Linear weights [out][in]; h = hidden_size // 2. */
+ * p_logvar = L(dx,h)-ReLU-L(h,dy)-Tanh; Linear weights [out][in]; h = hidden_size // 2.
+ * CV_MI_CLUBMEAN only: w3 = b3 = w4 = b4 = NULL (logvar == 0), in cv_mlp_grad as well. */
 typedef struct cv_mlp {
   const float *w1, *b1, *w2, *b2;   /* p_mu     */
   const float *w3, *b3, *w4, *b4;   /* p_logvar */
@@ -511,6 +518,39 @@ int cv_mi_learning_step(const cv_mlp* mlp, const float* x, int ldx, const float*
                         const float* grads,
                         float* exp_avg, float* exp_avg_sq, int64_t numel, const float* hyper,
                         int64_t* step, cv_stream_t stream);
+
+/* ---- InfoNCE lower bound (mi_estimator.py:245-273) ----
+ * critic F = Linear(dx+dy, h) -> ReLU -> Linear(h, 1) -> Softplus (mi_estimator.py:250-253), Linear weights
+ * [out][in]: w1 [h][dx+dy], b1 [h], w2 [h], b2 [1].  The [N, N, dx+dy] tiling of mi_estimator.py:262-266 factors
+ * through the first Linear (a_j = W1[:, :dx] x_j, c_i = W1[:, dx:] y_i + b1), so the kernels keep O(N h) memory. */
+typedef struct cv_critic {
+  const float *w1, *b1, *w2, *b2;
+  int dx, dy, h;
+} cv_critic;
+typedef struct cv_critic_grad {
+  float *w1, *b1, *w2, *b2;
+} cv_critic_grad;
+/* 1 when the kernels serve the geometry: 2 <= n <= 16384, 1 <= dx, dy, h <= 64 */
+int cv_infonce_supported(int n, int dx, int dy, int h);
+/* workspace of one estimator for batch n (zeroed once at allocation); linear in n */
+size_t cv_infonce_workspace_bytes(int n, int h);
+/* InfoNCE.forward (mi_estimator.py:259-270): out[0] = mean_i F(x_i, y_i) - (mean_i logsumexp_j F(x_j, y_i) - log n).
+ * Leaves the first-layer products and the row log-sum-exps in `work` for cv_infonce_backward. */
+int cv_infonce_forward(const cv_critic* critic, const float* x, int ldx, const float* y, int ldy, int n,
+                       void* work, float* out, cv_stream_t stream);
+/* gradient of gmul*gscale[0]*value (mi_estimator.py:259-270) w.r.t. x and y (written or accumulated) and, when
+ * g != NULL, the critic parameters (written, folded in fixed order).  Chain mode as cv_mi_backward.  Needs the
+ * `work` a cv_infonce_forward of the same inputs left. */
+int cv_infonce_backward(const cv_critic* critic, const float* x, int ldx, const float* y, int ldy, int n,
+                        void* work, const float* gscale, float gmul, float* dx, float* dy, int gld,
+                        int accumulate, const cv_critic_grad* g, const float* heads, const float* z,
+                        float* dheads, int d, cv_stream_t stream);
+/* learning_loss = -forward (mi_estimator.py:272-273): loss and critic gradients (overwritten); with
+ * params != NULL also the Adam update of the estimator arena (trainer.py:885-887), as cv_mi_learning_step. */
+int cv_infonce_learning_step(const cv_critic* critic, const float* x, int ldx, const float* y, int ldy, int n,
+                             void* work, float* loss_out, const cv_critic_grad* g, float* params,
+                             const float* grads, float* exp_avg, float* exp_avg_sq, int64_t numel,
+                             const float* hyper, int64_t* step, cv_stream_t stream);
 
 /* ---- CLEAR-TC factor discriminator (trainer.py:573-699, trainer_utils.py:133-138) ----
  * factor_cls = Linear(z, z) -> ReLU -> Linear(z, 1) -> Sigmoid, Linear weights [out][in]; z <= 64, even. */
