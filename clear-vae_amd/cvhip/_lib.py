@@ -34,6 +34,7 @@ SIM = {"cosine": 0, "l2": 1, "modified_l2": 2, "jeffrey": 3, "mahalanobis": 4}
 MI_NONE, MI_CLUBSAMPLE, MI_L1OUT, MI_CLUB, MI_VARUB, MI_CLUBMEAN, MI_INFONCE = 0, 1, 2, 3, 4, 5, 6  # CV_MI_*
 MMA_FP32, MMA_BF16 = 0, 1  # CV_MMA_*
 GROUP = {"MLVAE": 0, "GVAE": 1}  # CV_GROUP_*
+STYLE = {"identity": 0, "stripe": 1, "zigzag": 2, "canny_edges": 3, "scale": 4, "brightness": 5}  # CV_STYLE_*
 PRECISION = {"fp32": MMA_FP32, "bf16": MMA_BF16}
 
 
@@ -465,6 +466,11 @@ _SIGS = {
          _P(cv_lam_grad), c_void_p],
     ),
     "cv_lam_forward": (c_int, [_P(cv_lam), c_void_p, _P(cv_bn), c_int, c_void_p, c_void_p]),
+    "cv_style_mnist": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, _P(c_int), _P(c_int), c_void_p, c_void_p,
+         c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     "cv_adam_step": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],

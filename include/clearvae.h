@@ -769,6 +769,33 @@ int cv_lam_step(const cv_lam* P, const float* y, const cv_bn* bn, const int64_t*
  * statistics); writes nothing else.  One launch; any n >= 1; the other limits as for cv_lam_supported. */
 int cv_lam_forward(const cv_lam* P, const float* y, const cv_bn* bn, int n, float* logits, cv_stream_t stream);
 
+/* ---- Styled-MNIST generation (corruption_utils/corruptions.py:230 identity, :712-716 stripe, :665-704 zigzag with
+ * :202-221 line_from_points, :719-722 canny_edges, :602-622 scale, :455-466 brightness; the per-image style draw of
+ * data_utils.py:29-52 StyledMNISTGenerator and expr_utils.py:18-32 KStyledMNISTGenerator) ----
+ * One launch, one workgroup per image: images uint8 [n][28][28] (4-byte aligned) -> out fp32 [n][28][28] in [0, 255],
+ * the corruption functions' return values.  label: [n] int64 in [0, n_class) (the caller checks that; the kernel
+ * clamps); table: device fp32 [n_class][n_style], each row a probability vector; kind / severity: host arrays
+ * [n_style], kind one of CV_STYLE_*, severity in 1..5 for scale and brightness (ignored for the others).
+ * For image i, u = philox(seed, *offset ^ tag, i): the style is the first index whose cumulative probability in row
+ * label[i] exceeds u.x 2^-32 (the last style with non-zero probability catches rounding), the zigzag start row is
+ * r0 = floor(u.y 2^-32 27) and its slope index dr = floor(u.z 2^-32 10) - 5 (np.random.randint(0, 27) and
+ * randint(-5, 5)).  style_in int32 [n] / zz_in int32 [n][2] (or NULL) give the style / (r0, dr) instead (test hooks;
+ * clamped to their ranges); cand_in uint8 [n][28][28] (or NULL; test hook) gives canny images their candidate map
+ * (0 none, 1 weak, 2 strong) in place of the front end.  offset: device uint64[2] = (counter, arrival count = 0) or
+ * NULL = counter 0; the counter is advanced by one unless both style_in and zz_in are given.
+ * zz_pts: device fp64 [10][8][2], the (column, row) endpoints of the zigzag polyline for dr = -5..4 with r0 = 0;
+ * zz_cols: device int32 [10][7][2], every segment's (floor(c0), ceil(c1)) column range.
+ * style_out int64 [n]; zz_out int32 [n][2] = the (r0, dr) of every image (used by its zigzag, if that is its style).
+ * The canny and warp semantics are those DESIGN 4g writes out.  Every loop is bounded at compile time (the canny
+ * hysteresis: at most 784 sweeps).  Returns non-zero before any launch for a geometry other than 28x28, n_style
+ * outside 1..16, n <= 0, an unknown kind, a severity outside 1..5 or a missing pointer. */
+enum { CV_STYLE_IDENTITY = 0, CV_STYLE_STRIPE = 1, CV_STYLE_ZIGZAG = 2, CV_STYLE_CANNY = 3, CV_STYLE_SCALE = 4,
+       CV_STYLE_BRIGHTNESS = 5 };
+int cv_style_mnist(const uint8_t* images, int n, int h, int w, const int64_t* label, const float* table, int n_class,
+                   int n_style, const int* kind, const int* severity, const double* zz_pts, const int32_t* zz_cols,
+                   uint64_t seed, uint64_t* offset, const int32_t* style_in, const int32_t* zz_in,
+                   const uint8_t* cand_in, float* out, int64_t* style_out, int32_t* zz_out, cv_stream_t stream);
+
 /* ---- Adam (torch.optim.Adam foreach semantics) over a flat fp32 arena ----
  * hyper: device float[8] = lr, beta1, beta2, eps, weight_decay; step: device int64[2] =
  * (steps taken, arrival counter = 0).  grad_scale (device float or NULL) multiplies the gradient
