@@ -13,7 +13,7 @@ namespace cv {
 
 // ---------------------------------------------------------------- host error plumbing
 void set_error(const char* fmt, ...);
-// launch log (cv_debug_kernel_log): the conv / linear launch sites record the kernel they issue
+// launch log (cv_debug_kernel_log): the conv / linear and NT-Xent launch sites record the kernel they issue
 void note_launch(const void* kernel);
 void clear_error();
 

@@ -816,6 +816,7 @@ static int ntxent_launch_lds(const NtArgs& a, int nbr, bool rows, hipStream_t st
     return -1;
   }
   void* params[] = {&arg};
+  note_launch(kern);
   if (hipLaunchKernel(kern, grid, dim3(256), params, lds, st) != hipSuccess) {
     ::cv::set_error("%s: launch failed", rows ? "ntxent_rows" : "ntxent_grad");
     return 2;
@@ -831,8 +832,9 @@ static int ntxent_launch(const NtArgs& a, int nbr, bool rows, hipStream_t st) {
     CV_LAUNCH_CHECK("latent_combine");
   }
   dim3 grid(cdiv(a.n, NT_ROWS), nbr);
-#define CV_NT_GLOBAL(DM_, BIG_)                                                          \
-  if (rows) hipLaunchKernelGGL((ntxent_rows_kernel<DM_, BIG_>), grid, dim3(256), 0, st, a); \
+#define CV_NT_GLOBAL(DM_, BIG_)                                                                              \
+  note_launch(rows ? (const void*)ntxent_rows_kernel<DM_, BIG_> : (const void*)ntxent_grad_kernel<DM_, BIG_>); \
+  if (rows) hipLaunchKernelGGL((ntxent_rows_kernel<DM_, BIG_>), grid, dim3(256), 0, st, a);                    \
   else hipLaunchKernelGGL((ntxent_grad_kernel<DM_, BIG_>), grid, dim3(256), 0, st, a);
 #define CV_NT_DM(BIG_)                           \
   if (a.d <= 8) { CV_NT_GLOBAL(8, BIG_) }        \
