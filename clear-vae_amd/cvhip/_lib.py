@@ -442,6 +442,21 @@ _SIGS = {
         [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p],
     ),
+    "cv_tsne_workspace_bytes": (c_size_t, [c_int]),
+    "cv_tsne_affinity": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    "cv_tsne_pair": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p],
+    ),
+    "cv_tsne_update": (
+        c_int,
+        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p],
+    ),
+    "cv_tsne_run": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
+         c_float, c_void_p, c_void_p, c_void_p],
+    ),
     "cv_probe_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "cv_probe_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cv_probe_step": (

@@ -655,7 +655,49 @@ int cv_rank_auc(const float* score, int lds, int n, int c, const int32_t* label,
                 const int32_t* start, uint32_t* counts_out, double* ap_sum_out, unsigned long long* u2_out, void* work,
                 cv_stream_t stream);
 
-/* ---- downstream probe (run_styledmnist_downstream_expr.py:110-117, trainer.py:125-131): the reference's `mlp` =
+/* ---- exact t-SNE for the latent plots (the demo notebooks and expr/visual_utils.py:144-183 call sklearn's
+ * TSNE(n_components=2, perplexity=30, learning_rate=200, init='pca').fit_transform on host copies of mu_c and mu_s);
+ * sklearn's method="exact" (manifold/_t_sne.py, _utils.pyx), matrix-free: O(n d) memory, no n x n array ----
+ * x: [n][d] fp32 with row stride ldx >= d, 1 <= d <= 64, 2 <= n <= 65536; d_ij = the squared Euclidean distance;
+ * the embedding y is [n][2] fp32.  Every sum is added in a fixed order and nothing uses atomics: all results are
+ * bit-reproducible.  work: cv_tsne_workspace_bytes(n) bytes (0 for n outside the limits), need not be zeroed;
+ * cv_tsne_pair fills it and cv_tsne_update reads it.
+ *
+ * cv_tsne_affinity (_utils.pyx _binary_search_perplexity, as _joint_probabilities calls it): per row i the precision
+ * beta_i of the conditional Gaussian with entropy H_i = ln(perplexity), 0 < perplexity < n, by sklearn's search
+ * (beta = 1; double / halve while the bracket is open, else the midpoint; at most 100 evaluations; stop at
+ * |H_i - ln perplexity| <= 1e-5), with H_i = ln S_i + beta_i sum_{j!=i} d_ij exp(-beta_i d_ij) / S_i and
+ * S_i = sum_{j!=i} exp(-beta_i d_ij), evaluated with every exponent shifted by the row's smallest distance.
+ * beta_out [n] = beta_i rounded to fp32, logz_out [n] = ln S_i at that rounded value.
+ *
+ * cv_tsne_pair (_t_sne.py _joint_probabilities:60-66 and _kl_divergence:130-178): with
+ * p_ij = max((exp(-beta_i d_ij - logz_i) + exp(-beta_j d_ij - logz_j)) / 2n, 2.220446e-16) and
+ * q_ij = 1 / (1 + |y_i - y_j|^2), the per-row sums over j != i of  e p q (y_i - y_j),  q^2 (y_i - y_j),  q  and,
+ * when with_kl,  e p (ln(e p) - ln q)  and  e p  (e = exaggeration > 0), one fp64 partial per slab of j, into work.
+ *
+ * cv_tsne_update (_t_sne.py _kl_divergence:170-178 and _gradient_descent:390-404): Z = sum_ij q_ij,
+ * grad_i = 4 (A_i - R_i / Z) -> grad_out [n][2] (or NULL), KL = sum e p ln(e p Z / q) -> kl_out (or NULL; only
+ * after a cv_tsne_pair with with_kl), and, when y is given, one descent step on y, update and gains ([n][2] each):
+ * gains += 0.2 where update * grad < 0, gains *= 0.8 elsewhere, gains >= 0.01,
+ * update = momentum * update - learning_rate * gains * grad, y += update.  reset != 0: update and gains are taken
+ * as 0 and 1 instead of being read.
+ *
+ * cv_tsne_run (_t_sne.py _tsne:1080-1130): n_iter rounds of pair + update on `stream`: exaggeration
+ * early_exaggeration and momentum 0.5 for the first exploration_iter rounds, then 1 and 0.8, with update and gains
+ * reset at round 0 and at the switch (sklearn starts a second _gradient_descent there); no early stopping.  With
+ * kl_out, one more pair pass stores the KL divergence of the final y (exaggeration 1). */
+size_t cv_tsne_workspace_bytes(int n);
+int cv_tsne_affinity(const float* x, int ldx, int n, int d, double perplexity, float* beta_out, float* logz_out,
+                     cv_stream_t stream);
+int cv_tsne_pair(const float* x, int ldx, int n, int d, const float* beta, const float* logz, const float* y,
+                 float exaggeration, int with_kl, void* work, cv_stream_t stream);
+int cv_tsne_update(int n, void* work, float* y, float* update, float* gains, float momentum, float learning_rate,
+                   int reset, float* grad_out, double* kl_out, cv_stream_t stream);
+int cv_tsne_run(const float* x, int ldx, int n, int d, const float* beta, const float* logz, float* y, float* update,
+                float* gains, int n_iter, int exploration_iter, float early_exaggeration, float learning_rate,
+                void* work, double* kl_out, cv_stream_t stream);
+
+/* ---- downstream probe(run_styledmnist_downstream_expr.py:110-117, trainer.py:125-131): the reference's `mlp` =
  * Linear(d,h) -> BatchNorm1d(h) -> ReLU -> Linear(h,c) on mu_c of the frozen VAE, nn.CrossEntropyLoss() defaults ----
  * Linear weights [out][in]; running statistics are the module's own buffers (updated in place by a training step:
  * momentum, unbiased running_var; nbt += 1 when given). */
