@@ -34,6 +34,8 @@ SIM = {"cosine": 0, "l2": 1, "modified_l2": 2, "jeffrey": 3, "mahalanobis": 4}
 MI_NONE, MI_CLUBSAMPLE, MI_L1OUT, MI_CLUB, MI_VARUB, MI_CLUBMEAN, MI_INFONCE = 0, 1, 2, 3, 4, 5, 6  # CV_MI_*
 MMA_FP32, MMA_BF16 = 0, 1  # CV_MMA_*
 GROUP = {"MLVAE": 0, "GVAE": 1}  # CV_GROUP_*
+SUPCON = {"supcon_in_loss": 0, "supcon_out_loss": 1}  # CV_SUPCON_IN / CV_SUPCON_OUT
+SUPCON_IN, SUPCON_OUT = 0, 1
 STYLE = {"identity": 0, "stripe": 1, "zigzag": 2, "canny_edges": 3, "scale": 4, "brightness": 5}  # CV_STYLE_*
 PRECISION = {"fp32": MMA_FP32, "bf16": MMA_BF16}
 
@@ -133,6 +135,27 @@ class cv_ntxent_branch(ctypes.Structure):
         ("gmul", c_float),
         ("loss_out", c_void_p),
         ("lse", c_void_p),
+    ]
+
+
+class cv_supcon_args(ctypes.Structure):
+    _fields_ = [
+        ("mu", c_void_p),
+        ("logvar", c_void_p),
+        ("ld", c_int),
+        ("label", c_void_p),
+        ("n", c_int),
+        ("d", c_int),
+        ("sim", c_int),
+        ("ps", c_int),
+        ("kind", c_int),
+        ("temperature", c_float),
+        ("stats", c_void_p),
+        ("loss_out", c_void_p),
+        ("dmu", c_void_p),
+        ("dlogvar", c_void_p),
+        ("gld", c_int),
+        ("gscale", c_void_p),
     ]
 
 
@@ -369,6 +392,9 @@ _SIGS = {
         [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
          c_void_p, _P(cv_ntxent_branch), c_int, c_void_p, c_int, c_float, c_void_p],
     ),
+    "cv_supcon_supported": (c_int, [c_int, c_int, c_int]),
+    "cv_supcon_stats_floats": (c_size_t, [c_int]),
+    "cv_supcon": (c_int, [_P(cv_supcon_args), c_int, c_void_p]),
     "cv_tc_workspace_bytes": (c_size_t, [c_int]),
     "cv_tc_forward": (
         c_int,

@@ -13,7 +13,8 @@ from __future__ import annotations
 import torch
 
 from . import _lib, rng
-from ._lib import GROUP, MI_CLUBSAMPLE, SIM, cv_critic, cv_critic_grad, cv_mlp, cv_mlp_grad, cv_ntxent_branch
+from ._lib import (GROUP, MI_CLUBSAMPLE, SIM, cv_critic, cv_critic_grad, cv_mlp, cv_mlp_grad, cv_ntxent_branch,
+                   cv_supcon_args)
 from .plan import Program, Workspace, ensure_arena, pack_program
 
 
@@ -350,6 +351,54 @@ class ContrastiveFn(torch.autograd.Function):
                               dlv.data_ptr(), d, gg.data_ptr(), 1.0, None, lse.data_ptr())
         _lib.call("cv_ntxent", br, 1, lab.data_ptr(), n, d, sim, tau, 1, 0, _lib.stream_handle())
         return dmu, (dlv if has_lv else None), None, None, None, None
+
+
+class SupConFn(torch.autograd.Function):
+    """contrastive_loss(mu, logvar, label, sim_fn, temperature, "supcon_in_loss" | "supcon_out_loss", ps)
+    (losses.py:98-126 over :140-170) as cv_supcon: phase 0 in forward (row statistics + loss), phase 1 in backward.
+    kind: _lib.SUPCON_IN / _lib.SUPCON_OUT."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, label, sim_fn, temperature, ps, kind):
+        if sim_fn not in SIM:
+            raise ValueError("unimplemented similarity measure.")
+        m, ld = _rows(mu)
+        if logvar is not None:
+            l_ = logvar if (logvar.dtype == torch.float32 and logvar.dim() == 2 and logvar.stride(0) == ld
+                            and logvar.stride(1) == 1) else None
+            if l_ is None:
+                m = _f32c(mu)
+                ld = m.stride(0)
+                l_ = _f32c(logvar)
+                assert l_.stride(0) == ld
+        else:
+            l_ = None
+        lab = label.reshape(-1).to(torch.int64).contiguous()
+        n, d = m.shape
+        if n == 1:  # (a one-row view may report any stride)
+            ld = max(ld, d)
+        stats = torch.empty(int(_lib.lib().cv_supcon_stats_floats(n)), dtype=torch.float32, device=m.device)
+        loss = torch.empty((), dtype=torch.float32, device=m.device)
+        a = cv_supcon_args(m.data_ptr(), l_.data_ptr() if l_ is not None else None, ld, lab.data_ptr(), n, d,
+                           SIM[sim_fn], int(bool(ps)), int(kind), float(temperature), stats.data_ptr(),
+                           loss.data_ptr(), None, None, 0, None)
+        _lib.call("cv_supcon", a, 0, _lib.stream_handle())
+        ctx.save_for_backward(m, l_ if l_ is not None else m, lab, stats)
+        ctx.meta = (ld, SIM[sim_fn], float(temperature), int(bool(ps)), int(kind), l_ is not None)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        m, l_, lab, stats = ctx.saved_tensors
+        ld, sim, tau, ps, kind, has_lv = ctx.meta
+        n, d = m.shape
+        dmu = torch.empty(n, d, dtype=torch.float32, device=m.device)
+        dlv = torch.empty(n, d, dtype=torch.float32, device=m.device)
+        gg = _f32c(g.reshape(1))
+        a = cv_supcon_args(m.data_ptr(), l_.data_ptr() if has_lv else None, ld, lab.data_ptr(), n, d, sim, ps, kind,
+                           tau, stats.data_ptr(), None, dmu.data_ptr(), dlv.data_ptr(), d, gg.data_ptr())
+        _lib.call("cv_supcon", a, 1, _lib.stream_handle())
+        return dmu, (dlv if has_lv else None), None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------- MI estimators

@@ -3,16 +3,21 @@
 Hot path — HIP kernels through cvhip.autograd:
   vae_loss           -> cv_mse_sum + cv_kl          (losses.py:36-50)
   contrastive_loss   -> cv_ntxent, all five sims    (losses.py:98-137)
-The pairwise_* / snn_loss / logsumexp helpers keep the reference's tensor-level semantics for
-callers that use them directly (they are building blocks, not the trained path); the supcon / lam
-losses and the sklearn metrics are outside the hot path and stay as in the
-reference (sklearn on CPU); gMIG also has a device backend (cv_knn_mi through cvhip.metrics), chosen
-per call or with the environment variable CVHIP_GMIG, and so does auc (cv_rank_auc, CVHIP_AUC).
+                        "supcon_in_loss" / "supcon_out_loss" with backend="device" -> cv_supcon (losses.py:140-170)
+The pairwise_* / snn_loss / supcon_*_loss / logsumexp helpers keep the reference's tensor-level semantics for
+callers that use them directly (they are building blocks, not the trained path); the lam loss and the
+sklearn metrics are outside the hot path (SURVEY 2, row 2b) and stay as in the reference (sklearn on CPU);
+gMIG also has a device backend (cv_knn_mi through cvhip.metrics), chosen per call or with the environment
+variable CVHIP_GMIG, and so does auc (cv_rank_auc, CVHIP_AUC).  The two supcon names of contrastive_loss
+default to the reference's torch composition (backend="torch"); backend="device", or CVHIP_SUPCON=device,
+runs them as HIP kernels in O(n d) memory (cvhip.autograd.SupConFn), which is what CLEARVAETrainer does when
+its hyperparameter "loss_name" is one of them.
 """
 
 from __future__ import annotations
 
 import os
+import warnings
 
 import torch
 import torch.nn.functional as F
@@ -138,16 +143,43 @@ def logsumexp(x: Tensor, dim: int) -> Tensor:
 # ----------------------------------------------------------------------------- contrastive
 
 
+SUPCON_BACKENDS = ("torch", "device")
+LOSS_NAMES = ("snn_loss", "supcon_in_loss", "supcon_out_loss")
+_warned_supcon = False
+
+
 def contrastive_loss(mu: torch.Tensor, logvar: torch.Tensor, label: torch.Tensor, sim_fn: str,
-                     temperature: float, loss_name: str = "snn_loss", ps: bool = False):
-    """SNN contrastive loss of losses.py:98-126 as one fused HIP op (cv_ntxent): similarity, label
-    masks, masked log-sum-exps and the mean over finite rows, with its analytic backward."""
+                     temperature: float, loss_name: str = "snn_loss", ps: bool = False, backend=None):
+    """Contrastive loss of losses.py:98-126.  "snn_loss" is one fused HIP op (cv_ntxent): similarity, label
+    masks, masked log-sum-exps and the mean over finite rows, with its analytic backward.
+
+    "supcon_in_loss" / "supcon_out_loss" (losses.py:140-170) take a backend: "torch" (the default) is the
+    reference's own composition as torch ops on the caller's tensors ([n, n] and, for three similarities, [n, n, d]
+    intermediates); "device" is the same value as HIP kernels in O(n d) memory (cv_supcon through
+    cvhip.autograd.SupConFn), for tensors on the ROCm device.  backend=None takes the environment variable
+    CVHIP_SUPCON when it is set, else "torch".  Wider than d = 64 the device backend warns once and runs the torch
+    composition.  "snn_loss" has no torch backend: naming one raises, and the environment variable is ignored."""
     if sim_fn not in SIM:
         raise ValueError("unimplemented similarity measure.")
     if loss_name in ("supcon_in_loss", "supcon_out_loss"):
-        # Off the trained path (no trainer or script passes them: SURVEY 2b): the reference's own composition
-        # (losses.py:107-126 with its eval(loss_name) dispatch) over the pairwise / supcon functions below, as
-        # torch ops on the caller's tensors, so a caller naming them gets the reference's values.
+        if backend is None:
+            backend = os.environ.get("CVHIP_SUPCON") or "torch"
+        if backend not in SUPCON_BACKENDS:
+            raise ValueError(f"contrastive_loss: unknown backend {backend!r} (one of {', '.join(SUPCON_BACKENDS)})")
+        if backend == "device":
+            _ag._require_gpu(mu, logvar, label)
+            from cvhip import _lib
+
+            n, d = mu.shape
+            if _lib.lib().cv_supcon_supported(int(n), int(d), SIM[sim_fn]):
+                return _ag.SupConFn.apply(mu, logvar, label, sim_fn, temperature, bool(ps), _lib.SUPCON[loss_name])
+            global _warned_supcon
+            if not _warned_supcon:
+                _warned_supcon = True
+                warnings.warn(f"contrastive_loss: n={n}, d={d} is outside the device kernels' envelope "
+                              "(1 <= n <= 131072, 1 <= d <= 64); running the torch composition")
+        # The reference's own composition (losses.py:107-126 with its eval(loss_name) dispatch) over the pairwise /
+        # supcon functions below, as torch ops on the caller's tensors.
         pair_mat = (label[None, :] != label[:, None]).float() if ps else (label[None, :] == label[:, None]).float()
         sim = {"cosine": lambda: pairwise_cosine(mu), "l2": lambda: pairwise_l2(mu),
                "modified_l2": lambda: pairwise_modified_l2_dis(mu, logvar),
@@ -157,6 +189,10 @@ def contrastive_loss(mu: torch.Tensor, logvar: torch.Tensor, label: torch.Tensor
         return losses[torch.isfinite(losses)].mean()
     if loss_name != "snn_loss":
         raise NameError(f"name '{loss_name}' is not defined")  # (what the reference's eval(loss_name) raises)
+    if backend is not None and backend != "device":
+        if backend not in SUPCON_BACKENDS:
+            raise ValueError(f"contrastive_loss: unknown backend {backend!r} (one of {', '.join(SUPCON_BACKENDS)})")
+        raise ValueError("contrastive_loss: snn_loss has no torch backend (it is always the device kernel cv_ntxent)")
     _ag._require_gpu(mu, logvar, label)
     return _ag.ContrastiveFn.apply(mu, logvar, label, sim_fn, temperature, bool(ps))
 

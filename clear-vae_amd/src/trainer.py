@@ -33,7 +33,7 @@ from torch.optim.optimizer import Optimizer
 from torch.utils.data import DataLoader
 from tqdm import tqdm
 
-from src.losses import accurary, auc, contrastive_loss, lam_loss, mutual_info_gap, vae_loss
+from src.losses import LOSS_NAMES, accurary, auc, contrastive_loss, lam_loss, mutual_info_gap, vae_loss
 from src.models.vae import VAE
 
 
@@ -118,7 +118,7 @@ class _ClearEval:
                 X_hat, lp, z = vae(X, explicit=True)
                 rec, kl_c, kl_s = vae_loss(X_hat, X, **lp)
                 c_loss = contrastive_loss(mu=lp["mu_c"], logvar=lp["logvar_c"], label=label, sim_fn=self.sim_fn,
-                                          temperature=hp["temperature"])
+                                          temperature=hp["temperature"], **getattr(self, "_loss_kw", {}))
                 last = last_fn(lp, label, z)
                 for i, v in enumerate((rec, kl_c, kl_s, c_loss, last)):
                     totals[i] += v
@@ -146,9 +146,22 @@ class CLEARVAETrainer(VAETrainer, _ClearEval):
                                          beta=hyperparameter["beta"])
         self._engine = None
         self.use_fused = True
+        # "loss_name" (not a key of the reference's dict; default its snn_loss): a supcon name trains with the device
+        # SupCon kernels (src.losses.contrastive_loss, backend="device") on the module path, without the fused engine
+        self.loss_name = hyperparameter.get("loss_name", "snn_loss")
+        if self.loss_name not in LOSS_NAMES:
+            raise NameError(f"name '{self.loss_name}' is not defined")
+        self._loss_kw = {} if self.loss_name == "snn_loss" else {"loss_name": self.loss_name, "backend": "device"}
+        self._check_single_process()
+
+    def _check_single_process(self):
+        if self._loss_kw and torch.distributed.is_available() and torch.distributed.is_initialized() \
+                and torch.distributed.get_world_size() > 1:
+            raise NotImplementedError(f"CLEARVAETrainer: loss_name={self.loss_name!r} is not data parallel "
+                                      "(only snn_loss has a fused multi-device step)")
 
     def _fused(self):
-        if not self.use_fused:
+        if not self.use_fused or self._loss_kw:
             return None
         from cvhip.engine import ClearStep
 
@@ -160,6 +173,7 @@ class CLEARVAETrainer(VAETrainer, _ClearEval):
         vae = self.model
         vae.train()
         hp = self.hyperparameter
+        self._check_single_process()
         engine = self._fused()
         with tqdm(dataloader, unit="batch", mininterval=0, disable=not verbose) as bar:
             bar.set_description(f"Epoch {epoch_id}")
@@ -183,9 +197,9 @@ class CLEARVAETrainer(VAETrainer, _ClearEval):
                 X_hat, lp = vae(X)
                 rec, kl_c, kl_s = vae_loss(X_hat, X, **lp)
                 c_loss = contrastive_loss(mu=lp["mu_c"], logvar=lp["logvar_c"], label=label, sim_fn=self.sim_fn,
-                                          temperature=hp["temperature"])
+                                          temperature=hp["temperature"], **self._loss_kw)
                 s_loss = contrastive_loss(mu=lp["mu_s"], logvar=lp["logvar_s"], label=label, sim_fn=self.sim_fn,
-                                          temperature=hp["temperature"], ps=hp["ps"])
+                                          temperature=hp["temperature"], ps=hp["ps"], **self._loss_kw)
                 if not hp["ps"]:
                     s_loss = -s_loss
                 loss = (rec + self.annealer(kl_c) + self.annealer(kl_s) + hp["alpha"] * c_loss
@@ -204,7 +218,7 @@ class CLEARVAETrainer(VAETrainer, _ClearEval):
 
         def s_term(lp, label, z):
             s = contrastive_loss(mu=lp["mu_s"], logvar=lp["logvar_s"], label=label, sim_fn=self.sim_fn,
-                                 temperature=hp["temperature"], ps=hp["ps"])
+                                 temperature=hp["temperature"], ps=hp["ps"], **self._loss_kw)
             return s if hp["ps"] else -s
 
         return self._evaluate(dataloader, verbose, epoch_id, "s_loss", s_term)

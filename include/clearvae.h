@@ -470,6 +470,37 @@ int cv_latent_step(const float* heads, const float* z, const float* dz, int n, i
                    float* dheads, float* losses, const cv_ntxent_branch* br, int nbr,
                    const int64_t* label, int sim, float temperature, cv_stream_t stream);
 
+/* ---- SupCon contrastive losses (losses.py:140-170, composed by contrastive_loss :98-126) ----
+ * S = pairwise_<sim>(mu, logvar), P_ij = [label_i == label_j] (ps: [label_i != label_j]), tau = temperature; cosine
+ * clamps each norm at 1e-8 as cv_ntxent does.  The reference's quirks are kept:
+ *   CV_SUPCON_IN  (losses.py:140-153): n_k[i] = sum_j P_ij - 1 — with ps the diagonal of P is 0, so that is one LESS
+ *     than the number of different-label rows; diagonal of S = -inf;
+ *     row_i = log n_k[i] - LSE_{j: P_ij, j != i}(S_ij / tau) + LSE_{j != i}(S_ij / tau).
+ *   CV_SUPCON_OUT (losses.py:156-170): diagonal of S = -999, a finite value that takes part in the log-sum-exp as
+ *     exp(-999 / tau) and carries no gradient; n_k[i] = the off-diagonal positives; rows with n_k = 0 are dropped;
+ *     row_i = -(sum_{j != i} P_ij S_ij) / n_k[i] + LSE_j(S_ij / tau): the first term is NOT divided by tau.
+ *   loss = the mean over the rows whose value is finite (losses.py:125-126); with no such row the loss is NaN and
+ *     every gradient element is exactly 0.
+ * Memory is O(n d): phase 0 writes per-row statistics into `stats` and the loss into loss_out; phase 1 reads them and
+ * writes gscale[0] * dloss / d(mu, logvar) (overwritten, never accumulated; dlogvar = 0 for cosine / l2).  No atomics:
+ * two runs give the same bits.  1 <= n <= 131072, 1 <= d <= 64, every CV_SIM_*, temperature > 0. */
+enum { CV_SUPCON_IN = 0, CV_SUPCON_OUT = 1 };
+typedef struct cv_supcon_args {
+  const float* mu; const float* logvar; int ld;   /* rows of stride ld; logvar NULL allowed for cosine / l2 */
+  const int64_t* label;
+  int n, d, sim, ps, kind;
+  float temperature;
+  float* stats;                                   /* [cv_supcon_stats_floats(n)]: phase 0 writes, phase 1 reads */
+  float* loss_out;                                /* [1], phase 0 */
+  float* dmu; float* dlogvar; int gld;            /* phase 1 outputs (dlogvar NULL allowed for cosine / l2) */
+  const float* gscale;                            /* [1] upstream gradient, device memory */
+} cv_supcon_args;
+/* 1 when the kernels serve the shape: the envelope above */
+int    cv_supcon_supported(int n, int d, int sim);
+/* floats of the stats workspace for batch n (linear in n) */
+size_t cv_supcon_stats_floats(int n);
+int    cv_supcon(const cv_supcon_args* a, int phase, cv_stream_t stream);   /* 0: rows + loss, 1: gradients */
+
 /* ---- MI upper bounds (mi_estimator.py:108-198; CLUB: mi_estimator.py:43-55, VarUB: mi_estimator.py:222-224) ---- */
 enum { CV_MI_NONE = 0, CV_MI_CLUBSAMPLE = 1, CV_MI_L1OUT = 2, CV_MI_CLUB = 3, CV_MI_VARUB = 4,
        /* CLUBMean (mi_estimator.py:65-105): CLUB with logvar == 0 and no p_logvar network; served by the cv_mi_*
