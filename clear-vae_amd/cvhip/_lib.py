@@ -37,6 +37,8 @@ GROUP = {"MLVAE": 0, "GVAE": 1}  # CV_GROUP_*
 SUPCON = {"supcon_in_loss": 0, "supcon_out_loss": 1}  # CV_SUPCON_IN / CV_SUPCON_OUT
 SUPCON_IN, SUPCON_OUT = 0, 1
 STYLE = {"identity": 0, "stripe": 1, "zigzag": 2, "canny_edges": 3, "scale": 4, "brightness": 5}  # CV_STYLE_*
+GRID_IMAGES, GRID_FILL = 0, 1  # CV_GRID_*
+FRAME = {None: 0, "red": 1, "blue": 2}  # CV_FRAME_*
 PRECISION = {"fp32": MMA_FP32, "bf16": MMA_BF16}
 
 
@@ -511,6 +513,14 @@ _SIGS = {
         c_int,
         [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, _P(c_int), _P(c_int), c_void_p, c_void_p,
          c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "cv_latent_pairs": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cv_latent_interp": (
+        c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "cv_make_grid": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_int, c_int,
+         ctypes.c_longlong, ctypes.c_longlong, c_int, c_int, c_void_p],
     ),
     "cv_adam_step": (
         c_int,

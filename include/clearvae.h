@@ -869,6 +869,52 @@ int cv_style_mnist(const uint8_t* images, int n, int h, int w, const int64_t* la
                    uint64_t seed, uint64_t* offset, const int32_t* style_in, const int32_t* zz_in,
                    const uint8_t* cand_in, float* out, int64_t* style_out, int32_t* zz_out, cv_stream_t stream);
 
+/* ---- The swap and interpolation figures (expr/visual_utils.py:13-128; torchvision.utils.make_grid) ----
+ * Three data-movement kernels, one launch per call, no atomics (the same inputs give the same bits).  Every
+ * host-side check fails with a non-zero return before anything is launched.
+ *
+ * cv_latent_pairs (visual_utils.py:34-36, the repeat / repeat / cat of feature_swapping_plot): z_c [n][dc] with row
+ * stride ldc, z_s [n][ds] with row stride lds (elements; column slices of one [n][dc + ds] array pass as they are)
+ * -> out, contiguous [n * n][dc + ds]: row i * n + j = (z_c[i], z_s[j]), copied bit for bit.  n * n * (dc + ds) must
+ * be below 2^31. */
+int cv_latent_pairs(const float* z_c, int ldc, const float* z_s, int lds, int n, int dc, int ds, float* out,
+                    cv_stream_t stream);
+/* cv_latent_interp (visual_utils.py:86-105 with display_utils.py:11-21 interpolate_latent): z [n][d] with row stride
+ * ldz; content = columns [0, z_dim), style = [z_dim, d); src_ids / tgt_ids: device int64 [s]; out, contiguous
+ * [2][s][steps][d].  With z1 = z[src_ids[i]], z2 = z[tgt_ids[i]] and p = torch.linspace(1, 0, steps) formed in fp32
+ * as torch forms it (step = -1 / (steps - 1); p_k = 1 + step k in the first half, 0 - step (steps - 1 - k) in the
+ * second; steps = 1: p = [1]):
+ *   out[0][i][k] = (z1.content, p_k z1.style + (1 - p_k) z2.style)       the style interpolation
+ *   out[1][i][k] = (p_k z1.content + (1 - p_k) z2.content, z1.style)     the content interpolation
+ * The copied halves are bit-exact; for steps >= 2 the rows k = 0 and k = steps - 1 of the interpolated half are z1 and
+ * z2 bit for bit (finite inputs).  The caller checks the ids; a pair with an id outside [0, n) reads nothing and gets
+ * NaN rows.  2 * s * steps * d must be below 2^31. */
+int cv_latent_interp(const float* z, int ldz, int n, int d, int z_dim, const int64_t* src_ids, const int64_t* tgt_ids,
+                     int s, int steps, float* out, cv_stream_t stream);
+/* cv_make_grid (torchvision.utils.make_grid(images, nrow, padding, pad_value=...) without normalize / scale_each,
+ * with visual_utils.py:13-26 make_colored_grid folded in), written into a sub-rectangle of a canvas (the torch.cat
+ * of visual_utils.py:44-52 and :80-118): images fp32 [m][c][h][w], contiguous, c = 1 (written to all three channels)
+ * or 3.  xmaps = min(nrow, m), ymaps = ceil(m / xmaps); the grid is ymaps (h + padding) + padding high and
+ * xmaps (w + padding) + padding wide; image k = y xmaps + x starts at (y (h + padding) + padding,
+ * x (w + padding) + padding); everything else, the cells past m in a ragged last row included, is pad_value.
+ * m = 1 gives the image alone, without padding, as torchvision does.
+ * mode = CV_GRID_FILL (m = 0; images, c, nrow and padding are not looked at): an h x w rectangle of pad_value.
+ * frame, applied to the value about to be written, pad or pixel alike (NaN never matches):
+ *   CV_FRAME_RED   where channel 0 is 0.25, channel 0 becomes 1; channels 1 and 2 stay (the reference's second and
+ *                  third masked assignments test channel 0 after the first has changed it: the frame is
+ *                  (1, 0.25, 0.25))
+ *   CV_FRAME_BLUE  where channel 2 is 0.25, the pixel becomes (0, 0, 1)
+ * Destination: element (ch, y, x) of a [3][dst_h][dst_w] canvas lies at dst[ch chan_pitch + y row_pitch + x]; the
+ * grid's top left corner goes to (y0, x0); nothing outside the grid's rectangle is written.
+ * Rejected: a null pointer, c not 1 or 3, padding < 0, nrow < 1, m outside 1..65536 (0 for CV_GRID_FILL), h or w
+ * outside 1..4096 (CV_GRID_FILL: below 1), row_pitch < dst_w, chan_pitch < dst_h row_pitch, a rectangle that does not
+ * fit the destination, a destination that spans 2^31 elements or more. */
+enum { CV_GRID_IMAGES = 0, CV_GRID_FILL = 1 };
+enum { CV_FRAME_NONE = 0, CV_FRAME_RED = 1, CV_FRAME_BLUE = 2 };
+int cv_make_grid(const float* images, int m, int c, int h, int w, int nrow, int padding, float pad_value, int frame,
+                 int mode, float* dst, int dst_h, int dst_w, long long chan_pitch, long long row_pitch, int y0, int x0,
+                 cv_stream_t stream);
+
 /* ---- Adam (torch.optim.Adam foreach semantics) over a flat fp32 arena ----
  * hyper: device float[8] = lr, beta1, beta2, eps, weight_decay; step: device int64[2] =
  * (steps taken, arrival counter = 0).  grad_scale (device float or NULL) multiplies the gradient
