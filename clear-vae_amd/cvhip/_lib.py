@@ -551,6 +551,17 @@ _SIGS = {
     "cv_debug_kernel_names": (c_int, [ctypes.c_char_p, c_size_t]),
     "cv_gemm_workspace_bytes": (c_size_t, []),
     "cv_set_gemm_workspace": (c_int, [c_void_p, c_size_t]),
+    "cv_blobs": (
+        c_int,
+        [c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_int, c_int, c_int, _P(c_float), c_int, c_void_p, c_uint64,
+         c_void_p, c_void_p],
+    ),
+    "cv_snn_bounds_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cv_snn_bounds": (
+        c_int,
+        [c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_int, c_int, c_int, c_void_p, ctypes.c_longlong,
+         _P(c_float), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
 }
 
 EXPORTED = tuple(_SIGS)

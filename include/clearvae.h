@@ -1010,6 +1010,38 @@ int cv_debug_kernel_names(char* buf, size_t cap);
 size_t cv_gemm_workspace_bytes(void);
 int cv_set_gemm_workspace(void* work, size_t bytes);
 
+/* ---- the MI-bound study (code/mi_experiment.ipynb) ----
+ * cv_blobs replaces the notebook's code cell 3 (generate_gaussian_blobs) for B trials at once:
+ *   x[b*ld_trial + i*ld_row + k] = centers[i / (n / n_blobs)] + stds[b] * eps,   b < B, i < n, k < d
+ * with eps standard normal from the library's Philox4x32-10 + Box-Muller.  The strides select [B][n][d] storage
+ * (ld_row >= d, ld_trial >= n*ld_row) or [n][B][d] storage (ld_trial >= d, ld_row >= B*ld_trial); the element at
+ * position q of the storage order (padding not counted) takes normal (q & 1) of philox(seed, *offset ^ tag, q / 2),
+ * so both normals of a draw are used and the writes are contiguous in memory.  centers: host [n_blobs]; stds: device
+ * [B]; offset: device uint64[2] = (counter, arrival count = 0) or NULL = counter 0; the counter is advanced by one on
+ * the device (a captured graph draws fresh blobs at every replay).  Returns non-zero before any launch unless
+ * B >= 1, d >= 1, 1 <= n_blobs <= 16, n a positive multiple of n_blobs and the strides are one of the two forms. */
+int cv_blobs(float* x, long long ld_trial, long long ld_row, int B, int n, int d, const float* centers, int n_blobs,
+             const float* stds, uint64_t seed, uint64_t* offset, cv_stream_t stream);
+/* cv_snn_bounds replaces the notebook's code cells 1-2 (logsumexp, PSSNN, SNN; losses.py:98-137 with the cosine
+ * similarity) for B trials and T temperatures in one pass.  For trial b, row i, temperature tau, with
+ * u_j = x_j / max(|x_j|, 1e-8) and s_ij = u_i . u_j:
+ *   lse_all = log sum_{j != i} exp(s_ij / tau),  lse_pos over j != i with label_j == label_i,  lse_neg over
+ *   label_j != label_i (an empty set: -inf);  SNN row term = lse_all - lse_pos, PS-SNN row term = lse_all - lse_neg;
+ *   bound[b][t][0 SNN, 1 PS-SNN] = the mean of the finite row terms, count[b][t][.] = how many there are
+ *   (none: bound NaN, count 0, the mean of an empty tensor).
+ * A NaN or infinity in a trial makes that trial's bounds NaN with count 0 and touches no other trial.
+ * x: fp32, element (b, i, k) at x[b*ld_trial + i*ld_row + k]; label: int64 (compared as int64), label of (b, i) at
+ * label[b*ld_label + i] (ld_label = 0: one [n] vector for every trial); taus: host [T]; rows: NULL or fp32
+ * [B][T][3][n] = lse_all, lse_pos, lse_neg; work: cv_snn_bounds_workspace_bytes(B, n, T) bytes (0 outside the
+ * envelope), need not be zeroed.  Each pair is evaluated once for all temperatures; the sets keep running maxima
+ * of the similarity, so nothing underflows at small tau; no atomics, fixed summation orders: the same inputs give
+ * the same bits, and trial b of a batch has the bits of a B = 1 call on it.  Two launches.  Returns non-zero before
+ * any launch unless 2 <= n <= 65536, 1 <= d <= 64, 1 <= T <= 8, every tau finite and > 0, B >= 1, B*n < 2^31. */
+size_t cv_snn_bounds_workspace_bytes(int B, int n, int T);
+int cv_snn_bounds(const float* x, long long ld_trial, long long ld_row, int B, int n, int d, const int64_t* label,
+                  long long ld_label, const float* taus, int T, double* bound, int32_t* count, float* rows,
+                  void* work, cv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
