@@ -26,6 +26,14 @@
 // Variants (template FULL): the mu / logvar rows of the columns are staged in LDS with the odd pitch d + 1 (lanes on
 // consecutive rows hit distinct banks) — all n rows at once when sc_lds_bytes(n, ...) <= 144 KiB (FULL), else in
 // tiles of SC_TJ rows that every workgroup walks through (the global-walk variant, any n up to NT_MAXBIG).
+//
+// The step form, cv_supcon_step (the fused CLEAR step's two contrastive terms, reference trainer.py:456-480: the
+// content and the style branch of losses.py:98-126, 140-170 on the same labels): the same row / loss / gradient
+// bodies (sc_rows_body, sc_loss_body, cv_supcon_grad.inc) over up to two branches in one launch each, the branch index
+// as a grid dimension (sc_step_*_kernel), reading the [n][4d] heads in place through the row stride.  Its phase 1
+// (ACC in cv_supcon_grad.inc) ADDS gmul * gscale[0] * dloss / d theta
+// onto what dmu / dlogvar hold: lane k of row i's wave reads and writes element (i, k) of its branch, nobody else
+// does, so the sum has one order and two runs give the same bits; for cosine / l2 the logvar columns are not touched.
 #include "cv_ntxent.hpp"
 
 namespace cv {
@@ -43,6 +51,12 @@ struct ScArgs {
   float* dlv;
   int gld;
   const float* gscale;
+};
+
+struct ScStepArgs {  // cv_supcon_step: branch b is blockIdx.y
+  ScArgs br[2];
+  float gmul[2];
+  int nbr;
 };
 
 constexpr int SC_ROWS = 4;    // rows (waves) per 256-thread workgroup
@@ -103,7 +117,7 @@ __device__ __forceinline__ void sc_row(const ScArgs& A, int r, float* m, float* 
 
 // ---------------------------------------------------------------- phase 0: row statistics
 template <int DM, bool FULL>
-__global__ __launch_bounds__(256) void sc_rows_kernel(const ScArgs A) {
+__device__ __forceinline__ void sc_rows_body(const ScArgs& A) {
   extern __shared__ __attribute__((aligned(16))) char sc_smem[];
   const int n = A.n, d = A.d;
   const bool cosine = A.sim == CV_SIM_COSINE;
@@ -176,10 +190,18 @@ __global__ __launch_bounds__(256) void sc_rows_kernel(const ScArgs A) {
   st[5 * (size_t)n + i] = row;
 }
 
+template <int DM, bool FULL>
+__global__ __launch_bounds__(256) void sc_rows_kernel(const ScArgs A) {
+  sc_rows_body<DM, FULL>(A);
+}
+
+template <int DM, bool FULL>
+__global__ __launch_bounds__(256) void sc_step_rows_kernel(const ScStepArgs P) {
+  sc_rows_body<DM, FULL>(P.br[blockIdx.y]);
+}
+
 // the loss and the kept-row count: one workgroup, thread t folds rows t, t + 1024, ... in order, then a fixed tree
-__global__ __launch_bounds__(1024) void sc_loss_kernel(const ScArgs A) {
-  __shared__ double ssum[16];
-  __shared__ float scnt[16];
+__device__ __forceinline__ void sc_loss_body(const ScArgs& A, double* ssum, float* scnt) {
   const int n = A.n;
   const float* row = A.stats + 5 * (size_t)n;
   double s = 0.0;
@@ -199,100 +221,68 @@ __global__ __launch_bounds__(1024) void sc_loss_kernel(const ScArgs A) {
   }
 }
 
+__global__ __launch_bounds__(1024) void sc_loss_kernel(const ScArgs A) {
+  __shared__ double ssum[16];
+  __shared__ float scnt[16];
+  sc_loss_body(A, ssum, scnt);
+}
+
+__global__ __launch_bounds__(1024) void sc_step_loss_kernel(const ScStepArgs P) {  // one workgroup per branch
+  __shared__ double ssum[16];
+  __shared__ float scnt[16];
+  sc_loss_body(P.br[blockIdx.x], ssum, scnt);
+}
+
 // ---------------------------------------------------------------- phase 1: gradients
 template <int DM, bool FULL>
 __global__ __launch_bounds__(256) void sc_grad_kernel(const ScArgs A) {
-  extern __shared__ __attribute__((aligned(16))) char sc_smem[];
-  const int n = A.n, d = A.d;
-  const bool cosine = A.sim == CV_SIM_COSINE;
-  const bool need_lv = !(A.sim == CV_SIM_COSINE || A.sim == CV_SIM_L2);
-  const bool out = A.kind == CV_SUPCON_OUT;
-  const int T = FULL ? n : SC_TJ;
-  float* smu = reinterpret_cast<float*>(sc_smem);
-  float* slv = smu + (size_t)T * (d + 1);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i = blockIdx.x * SC_ROWS + w;
-  const bool valid = i < n;
-  const int ic = valid ? i : 0;
-  const float* __restrict__ st = A.stats;
-  const float m = st[6 * (size_t)n];
-  const float c = (m > 0.f) ? A.gscale[0] / m : 0.f;
-  const float inv_tau = 1.f / A.tau;
-  float mi[DM], li[DM], mj[DM], lj[DM], gm[DM], gl[DM];
-  sc_row<DM>(A, ic, mi, li, need_lv);
-#pragma unroll
-  for (int k = 0; k < DM; ++k) { gm[k] = 0.f; gl[k] = 0.f; }
-  const float rni = cosine ? reg_norm<DM>(mi, d) : 0.f;
-  const float ni = cosine ? fmaxf(rni, 1e-8f) : 1.f;
-  const bool clamped_i = cosine && !(rni > 1e-8f);
-  const int64_t lab = A.label[ic];
-  const float a0 = st[ic], a1 = st[(size_t)n + ic], a2 = st[2 * (size_t)n + ic], a3 = st[3 * (size_t)n + ic];
-  for (int j0 = 0; j0 < n; j0 += T) {
-    const int tn = min(T, n - j0);
-    if (j0) __syncthreads();
-    sc_stage(A, j0, tn, need_lv, smu, slv);
-    if (!valid) continue;
-    for (int jj = lane; jj < tn; jj += 64) {
-      const int j = j0 + jj;
-      if (j == i) continue;
-      sc_theta<DM>(smu, slv, jj, d, mj, lj, need_lv);
-      const float nj = cosine ? fmaxf(reg_norm<DM>(mj, d), 1e-8f) : 1.f;
-      const float S = sim_ij<DM>(A.sim, mi, li, ni, mj, lj, nj, d);
-      const float s = S / A.tau;
-      const int64_t lj_ = A.label[j];
-      const bool pos = A.ps ? (lj_ != lab) : (lj_ == lab);
-      const float b0 = st[j], b1 = st[(size_t)n + j], b2 = st[2 * (size_t)n + j], b3 = st[3 * (size_t)n + j];
-      // (a dropped row: max = +inf, 1 / n_k = 0, so each of its terms is exp(-inf) = 0 or 0)
-      float H = (expf((s - a0) - a1) + expf((s - b0) - b1)) * inv_tau;
-      if (pos) {
-        if (out) H -= a2 + b2;
-        else H -= (expf((s - a2) - a3) + expf((s - b2) - b3)) * inv_tau;
-      }
-      H *= c;
-      if (H != 0.f) sim_grad_row<DM>(A.sim, mi, li, ni, clamped_i, mj, lj, nj, S, H, d, gm, gl);
-    }
-  }
-  if (!valid) return;
-#pragma unroll
-  for (int k = 0; k < DM; ++k) {
-    if (k < d) {
-      gm[k] = wave_sum(gm[k]);
-      if (need_lv) gl[k] = wave_sum(gl[k]);
-    }
-  }
-  // lane k writes component k (one coalesced row store)
-  float om = 0.f, ol = 0.f;
-#pragma unroll
-  for (int k = 0; k < DM; ++k)
-    if (k == lane) { om = gm[k]; ol = need_lv ? gl[k] : 0.f; }
-  if (lane < d) {
-    A.dmu[(size_t)i * A.gld + lane] = om;
-    if (A.dlv) A.dlv[(size_t)i * A.gld + lane] = ol;
-  }
+  constexpr bool ACC = false;
+  const float gmul = 1.f;
+#include "cv_supcon_grad.inc"
 }
 
 template <int DM, bool FULL>
-static int sc_launch_t(const ScArgs& a, int phase, size_t lds, hipStream_t st) {
-  const void* kern = phase == 0 ? (const void*)sc_rows_kernel<DM, FULL> : (const void*)sc_grad_kernel<DM, FULL>;
+__global__ __launch_bounds__(256) void sc_step_grad_kernel(const ScStepArgs P) {
+  constexpr bool ACC = true;
+  const ScArgs A = P.br[blockIdx.y];  // (a copy: through a reference the tiled DM = 32 kernel spills 12 bytes)
+  const float gmul = P.gmul[blockIdx.y];
+#include "cv_supcon_grad.inc"
+}
+
+static int sc_launch(const void* kern, void* arg, dim3 grid, int phase, size_t lds, hipStream_t st) {
   if (lds > 64 * 1024 && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
     set_error("supcon: %zu bytes of LDS refused", lds);
     return 2;
   }
-  ScArgs arg = a;
-  void* params[] = {&arg};
+  void* params[] = {arg};
   note_launch(kern);
-  if (hipLaunchKernel(kern, dim3(cdiv(a.n, SC_ROWS)), dim3(256), params, lds, st) != hipSuccess) {
+  if (hipLaunchKernel(kern, grid, dim3(256), params, lds, st) != hipSuccess) {
     set_error("supcon: launch failed (phase %d)", phase);
     return 2;
   }
   return 0;
 }
 
-template <bool FULL>
-static int sc_launch_dm(const ScArgs& a, int phase, size_t lds, hipStream_t st) {
-  if (a.d <= 8) return sc_launch_t<8, FULL>(a, phase, lds, st);
-  if (a.d <= 16) return sc_launch_t<16, FULL>(a, phase, lds, st);
-  if (a.d <= 32) return sc_launch_t<32, FULL>(a, phase, lds, st);
+template <int DM, bool FULL>
+static int sc_launch_t(const ScArgs& a, int phase, size_t lds, hipStream_t st) {
+  const void* kern = phase == 0 ? (const void*)sc_rows_kernel<DM, FULL> : (const void*)sc_grad_kernel<DM, FULL>;
+  ScArgs arg = a;
+  return sc_launch(kern, &arg, dim3(cdiv(a.n, SC_ROWS)), phase, lds, st);
+}
+
+template <int DM, bool FULL>
+static int sc_launch_t(const ScStepArgs& a, int phase, size_t lds, hipStream_t st) {
+  const void* kern =
+      phase == 0 ? (const void*)sc_step_rows_kernel<DM, FULL> : (const void*)sc_step_grad_kernel<DM, FULL>;
+  ScStepArgs arg = a;
+  return sc_launch(kern, &arg, dim3(cdiv(a.br[0].n, SC_ROWS), a.nbr), phase, lds, st);
+}
+
+template <bool FULL, class Args>
+static int sc_launch_dm(const Args& a, int d, int phase, size_t lds, hipStream_t st) {
+  if (d <= 8) return sc_launch_t<8, FULL>(a, phase, lds, st);
+  if (d <= 16) return sc_launch_t<16, FULL>(a, phase, lds, st);
+  if (d <= 32) return sc_launch_t<32, FULL>(a, phase, lds, st);
   return sc_launch_t<64, FULL>(a, phase, lds, st);
 }
 
@@ -345,13 +335,74 @@ extern "C" int cv_supcon(const cv_supcon_args* p, int phase, cv_stream_t stream)
   a.gscale = p->gscale;
   const hipStream_t st = S(stream);
   const size_t full = sc_lds_bytes(a.n, a.d, need_lv);
-  const int rc = full <= SC_LDS_MAX ? sc_launch_dm<true>(a, phase, full, st)
-                                    : sc_launch_dm<false>(a, phase, sc_lds_bytes(SC_TJ, a.d, need_lv), st);
+  const int rc = full <= SC_LDS_MAX ? sc_launch_dm<true>(a, a.d, phase, full, st)
+                                    : sc_launch_dm<false>(a, a.d, phase, sc_lds_bytes(SC_TJ, a.d, need_lv), st);
   if (rc) return rc;
   if (phase == 0) {
     note_launch((const void*)sc_loss_kernel);
     hipLaunchKernelGGL(sc_loss_kernel, dim3(1), dim3(1024), 0, st, a);
     CV_LAUNCH_CHECK("supcon_loss");
+  }
+  return 0;
+}
+
+extern "C" int cv_supcon_step(const cv_supcon_branch* br, int nbr, const int64_t* label, int n, int d, int sim, int kind,
+                              float temperature, int phase, cv_stream_t stream) {
+  clear_error();
+  CV_REQUIRE(br, "supcon_step: null branches");
+  CV_REQUIRE(nbr == 1 || nbr == 2, "supcon_step: 1 or 2 branches (nbr=%d)", nbr);
+  CV_REQUIRE(phase == 0 || phase == 1, "supcon_step: phase must be 0 or 1 (phase=%d)", phase);
+  CV_REQUIRE(n >= 1 && n <= NT_MAXBIG, "supcon_step: batch must be in 1..%d (n=%d)", NT_MAXBIG, n);
+  CV_REQUIRE(d >= 1 && d <= 64, "supcon_step: width must be in 1..64 (d=%d)", d);
+  CV_REQUIRE(sim >= CV_SIM_COSINE && sim <= CV_SIM_MAHALANOBIS, "supcon_step: unknown similarity %d", sim);
+  CV_REQUIRE(kind == CV_SUPCON_IN || kind == CV_SUPCON_OUT, "supcon_step: unknown kind %d", kind);
+  CV_REQUIRE(label, "supcon_step: label is required");
+  CV_REQUIRE(temperature > 0.f, "supcon_step: temperature must be positive");
+  const bool need_lv = !(sim == CV_SIM_COSINE || sim == CV_SIM_L2);
+  ScStepArgs P;
+  P.nbr = nbr;
+  for (int b = 0; b < 2; ++b) {
+    const cv_supcon_branch& q = br[b < nbr ? b : 0];  // (an unused slot repeats branch 0: never indexed)
+    if (b < nbr) {
+      CV_REQUIRE(q.mu && q.stats, "supcon_step: branch %d: mu and stats are required", b);
+      CV_REQUIRE(!need_lv || q.logvar, "supcon_step: branch %d: this similarity reads logvar", b);
+      CV_REQUIRE(q.ld >= d, "supcon_step: branch %d: row stride %d < d=%d", b, q.ld, d);
+      if (phase == 0) CV_REQUIRE(q.loss_out, "supcon_step: branch %d: phase 0 needs loss_out", b);
+      if (phase == 1) {
+        CV_REQUIRE(q.dmu && q.gscale, "supcon_step: branch %d: phase 1 needs dmu and gscale", b);
+        CV_REQUIRE(q.gld >= d, "supcon_step: branch %d: gradient row stride %d < d=%d", b, q.gld, d);
+      }
+    }
+    ScArgs& a = P.br[b];
+    a.mu = q.mu;
+    a.lv = need_lv ? q.logvar : nullptr;
+    a.ld = q.ld;
+    a.label = label;
+    a.n = n;
+    a.d = d;
+    a.sim = sim;
+    a.ps = q.ps ? 1 : 0;
+    a.kind = kind;
+    a.tau = temperature;
+    a.stats = q.stats;
+    a.loss_out = q.loss_out;
+    a.dmu = q.dmu;
+    a.dlv = q.dlogvar;
+    a.gld = q.gld;
+    a.gscale = q.gscale;
+    P.gmul[b] = q.gmul;
+  }
+  if (nbr == 2)
+    CV_REQUIRE(br[0].stats != br[1].stats, "supcon_step: the branches need a stats workspace each");
+  const hipStream_t st = S(stream);
+  const size_t full = sc_lds_bytes(n, d, need_lv);
+  const int rc = full <= SC_LDS_MAX ? sc_launch_dm<true>(P, d, phase, full, st)
+                                    : sc_launch_dm<false>(P, d, phase, sc_lds_bytes(SC_TJ, d, need_lv), st);
+  if (rc) return rc;
+  if (phase == 0) {
+    note_launch((const void*)sc_step_loss_kernel);
+    hipLaunchKernelGGL(sc_step_loss_kernel, dim3(nbr), dim3(1024), 0, st, P);
+    CV_LAUNCH_CHECK("supcon_step_loss");
   }
   return 0;
 }

@@ -161,6 +161,22 @@ class cv_supcon_args(ctypes.Structure):
     ]
 
 
+class cv_supcon_branch(ctypes.Structure):
+    _fields_ = [
+        ("mu", c_void_p),
+        ("logvar", c_void_p),
+        ("ld", c_int),
+        ("ps", c_int),
+        ("dmu", c_void_p),
+        ("dlogvar", c_void_p),
+        ("gld", c_int),
+        ("gscale", c_void_p),
+        ("gmul", c_float),
+        ("loss_out", c_void_p),
+        ("stats", c_void_p),
+    ]
+
+
 class cv_mlp(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4")] + [
         ("dx", c_int),
@@ -397,6 +413,10 @@ _SIGS = {
     "cv_supcon_supported": (c_int, [c_int, c_int, c_int]),
     "cv_supcon_stats_floats": (c_size_t, [c_int]),
     "cv_supcon": (c_int, [_P(cv_supcon_args), c_int, c_void_p]),
+    "cv_supcon_step": (
+        c_int,
+        [_P(cv_supcon_branch), c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
+    ),
     "cv_tc_workspace_bytes": (c_size_t, [c_int]),
     "cv_tc_forward": (
         c_int,

@@ -44,8 +44,8 @@ import torch.distributed as dist
 
 from . import _lib, rng
 from . import dist as cvdist
-from ._lib import (GROUP, MI_CLUB, MI_CLUBMEAN, MI_CLUBSAMPLE, MI_INFONCE, MI_L1OUT, MI_VARUB, SIM, cv_critic_grad,
-                   cv_latent_chain, cv_mlp, cv_ntxent_branch, cv_tc_disc, cv_tc_grad)
+from ._lib import (GROUP, MI_CLUB, MI_CLUBMEAN, MI_CLUBSAMPLE, MI_INFONCE, MI_L1OUT, MI_VARUB, SIM, SUPCON,
+                   cv_critic_grad, cv_latent_chain, cv_mlp, cv_ntxent_branch, cv_supcon_branch, cv_tc_disc, cv_tc_grad)
 from .autograd import critic_struct, est_params, mlp_grad_struct, mlp_struct
 from ._lib import cv_conv_pack
 from .plan import (DeferGroup, ParamArena, Program, Workspace, ensure_arena, pack_program, ptr_array,
@@ -209,6 +209,8 @@ class _StepCtx:
     aux_args: list | None = None  # cv_ntxent_aux arguments of phases 0 and 1
     aux_comb: tuple | None = None  # cv_ntxent_aux_combine arguments (chain_nt)
     chain: object = None  # cv_latent_chain of the heads backward (chain_nt)
+    sc_arr: object = None  # the cv_supcon_branch array of a SupCon step (then br_arr is None and no aux placement)
+    sc_keep: tuple = ()  # ... its per-branch stats workspaces and the [1] upstream gradient
 
 
 class _AdamState:
@@ -308,6 +310,13 @@ class ClearStep:
                 return None
         elif trainer.sim_fn not in SIM:
             raise ValueError("unimplemented similarity measure.")
+        if mode == "clear" and getattr(trainer, "loss_name", "snn_loss") in SUPCON:
+            # the SupCon step: single process only (its data-parallel programs do not exist), within cv_supcon's widths
+            if _dist_world() > 1 or (os.environ.get("CVHIP_FORCE_DP", "0") == "1" and dist.is_available()
+                                     and dist.is_initialized()):
+                return None
+            if not _lib.lib().cv_supcon_supported(2, vae._cv_spec.d, SIM[trainer.sim_fn]):
+                return None
         if mode == "mim":
             from src.models.mi_estimator import CLUB, CLUBMean, CLUBSample, InfoNCE, L1OutUB, VarUB
 
@@ -346,6 +355,9 @@ class ClearStep:
         self.hp = dict(hp)
         self.sim = SIM[trainer.sim_fn] if mode != "group" else 0
         self.group_mode = GROUP[self.vae.mode] if mode == "group" else None
+        # CV_SUPCON_* when the CLEAR trainer's loss_name is a SupCon one (the step's contrastive terms are then
+        # cv_supcon_step's instead of the NT-Xent phases), else None
+        self.supcon = SUPCON.get(getattr(trainer, "loss_name", "snn_loss")) if mode == "clear" else None
         self.anneal = torch.tensor([trainer.annealer.current_step], dtype=torch.int64, device=self.device)
         self.anneal_expected = trainer.annealer.current_step
         # the shared (device, seed) Philox counter: engine rebuilds and the module path (evaluate, fallback
@@ -504,6 +516,21 @@ class ClearStep:
         # gradients into d(heads)
         hb, dh = ws.heads.data_ptr(), ws.dheads.data_ptr()
         alpha = float(hp["alpha"])
+        if self.supcon is not None:
+            # the same two branches as cv_supcon_branch entries, a stats workspace each; no NT-Xent branch array and
+            # no aux placement: the phases follow the KL + decoder-chain seed in `lat` and accumulate onto it
+            ps = bool(hp["ps"])
+            stats = torch.zeros(2, int(_lib.lib().cv_supcon_stats_floats(n)), dtype=torch.float32, device=dev)
+            one = torch.ones(1, dtype=torch.float32, device=dev)
+            lp = ws.losses.data_ptr()
+            ctx.sc_arr = (cv_supcon_branch * 2)(
+                cv_supcon_branch(hb, hb + 4 * d, 4 * d, 0, dh, dh + 4 * d, 4 * d, one.data_ptr(), alpha, lp + 12,
+                                 stats[0].data_ptr()),
+                cv_supcon_branch(hb + 8 * d, hb + 12 * d, 4 * d, int(ps), dh + 8 * d, dh + 12 * d, 4 * d,
+                                 one.data_ptr(), alpha if ps else -alpha, lp + 16, stats[1].data_ptr()))
+            ctx.sc_keep = (stats, one)
+            ctx.det_dz = DET_DZ and ws.fused_decoder_input()
+            return ctx
         branches = [cv_ntxent_branch(hb, hb + 4 * d, 4 * d, 0, dh, dh + 4 * d, 4 * d, None, alpha,
                                      ws.losses.data_ptr() + 12, ws.lse[0].data_ptr())]
         if self.mode == "clear":
@@ -585,6 +612,21 @@ class ClearStep:
             lat.add("cv_group_backward", self.group_mode, ws.heads, ws.z, ws.dz, ctx.gwork, n, d, *self._kl_args(),
                     self.anneal, ws.rec, ws.dheads, ws.losses)
             lat.keep.append(ctx.gwork)
+            return lat, lat
+        if self.supcon is not None:
+            # the KL + decoder-chain seed OVERWRITES d(heads) (with dz = d(h) W in fixed order where the decoder-input
+            # backward left it to the combine), then the two SupCon branches accumulate on top: three launches
+            if ctx.det_dz:
+                lat.add("cv_latent_combine_dz", ws.heads, ws.z, ws.gah, sp.dec_lin.weight,
+                        ws.decoder_input_geometry(), *self._kl_args(), self.anneal, ws.rec, ws.dheads, ws.losses,
+                        ws.dz, 0, ws.comb_dz_work)
+            else:
+                lat.add("cv_latent_combine", ws.heads, ws.z, ws.dz, n, d, *self._kl_args(), self.anneal, ws.rec,
+                        ws.dheads, ws.losses, ws.comb_work)
+            for phase in (0, 1):
+                lat.add("cv_supcon_step", ctx.sc_arr, 2, ctx.lab, n, d, self.sim, self.supcon,
+                        ctypes.c_float(float(hp["temperature"])), phase)
+            lat.keep += [ctx.sc_arr, *ctx.sc_keep]
             return lat, lat
         if ctx.chain_nt:  # (the combine's two parts ride in the rows-phase grid and in the heads backward)
             pass

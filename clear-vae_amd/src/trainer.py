@@ -136,6 +136,9 @@ class _ClearEval:
         return mig, mse
 
 
+LOSS_STEPS = ("module", "fused")  # hyperparameter["loss_step"] / CVHIP_SUPCON_STEP of a supcon loss_name
+
+
 class CLEARVAETrainer(VAETrainer, _ClearEval):
     def __init__(self, model: VAE, optimizer: Optimizer, sim_fn: str, hyperparameter: dict[str, float],
                  verbose_period: int, device: torch.device, transform=None) -> None:
@@ -147,12 +150,27 @@ class CLEARVAETrainer(VAETrainer, _ClearEval):
         self._engine = None
         self.use_fused = True
         # "loss_name" (not a key of the reference's dict; default its snn_loss): a supcon name trains with the device
-        # SupCon kernels (src.losses.contrastive_loss, backend="device") on the module path, without the fused engine
+        # SupCon kernels (src.losses.contrastive_loss, backend="device") on the module path, or, opted in with
+        # "loss_step": "fused" (absent: the environment's CVHIP_SUPCON_STEP, absent too: "module"), as the fused
+        # engine's one-graph step (cvhip.engine.ClearStep with cv_supcon_step).  snn_loss ignores the key: its step
+        # is always the fused one.
         self.loss_name = hyperparameter.get("loss_name", "snn_loss")
         if self.loss_name not in LOSS_NAMES:
             raise NameError(f"name '{self.loss_name}' is not defined")
         self._loss_kw = {} if self.loss_name == "snn_loss" else {"loss_name": self.loss_name, "backend": "device"}
+        if hyperparameter.get("loss_step") not in (None,) + LOSS_STEPS:
+            raise ValueError(f"loss_step must be one of {LOSS_STEPS}, not {hyperparameter.get('loss_step')!r}")
         self._check_single_process()
+
+    def loss_step(self) -> str:
+        """How a supcon loss_name trains, "module" or "fused": the hyperparameter, else CVHIP_SUPCON_STEP, else
+        "module"; read when the step is asked for, so the environment may change between epochs."""
+        step = self.hyperparameter.get("loss_step")
+        if step is None:
+            step = os.environ.get("CVHIP_SUPCON_STEP", "module")
+        if step not in LOSS_STEPS:
+            raise ValueError(f"loss_step / CVHIP_SUPCON_STEP must be one of {LOSS_STEPS}, not {step!r}")
+        return step
 
     def _check_single_process(self):
         if self._loss_kw and torch.distributed.is_available() and torch.distributed.is_initialized() \
@@ -161,7 +179,7 @@ class CLEARVAETrainer(VAETrainer, _ClearEval):
                                       "(only snn_loss has a fused multi-device step)")
 
     def _fused(self):
-        if not self.use_fused or self._loss_kw:
+        if not self.use_fused or (self._loss_kw and self.loss_step() != "fused"):
             return None
         from cvhip.engine import ClearStep
 

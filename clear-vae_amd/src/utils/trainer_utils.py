@@ -61,18 +61,21 @@ def get_hierarchical_vae_trainer(beta, vae_lr, z_dim, group_mode, device, vae_ar
 
 def get_clearvae_trainer(beta, ps, vae_lr, z_dim, alpha, temperature, device, vae_arch: str = "VAE",
                          in_channel: int = 1, verbose_period: int = 5, precision: str = "fp32",
-                         loss_name: str = "snn_loss"):
+                         loss_name: str = "snn_loss", loss_step: str | None = None):
     """(trainer_utils.py:87-116).  `precision` (not in the reference, default its fp32): "bf16" runs the
     conv / linear contractions on bf16 MFMA operands (cvhip.plan.set_precision).  `loss_name` (not in the
     reference's factory either; its contrastive_loss takes it): "supcon_in_loss" / "supcon_out_loss" train with the
     device SupCon kernels on the module path; the key enters the hyperparameter dict only when it is not the
-    default."""
+    default.  `loss_step` ("module" / "fused", a supcon loss_name only; None: CVHIP_SUPCON_STEP, else "module"):
+    "fused" trains a supcon loss as the fused engine's one-graph step; the key enters the dict only when given."""
     vae = _resolve(vae_arch)(total_z_dim=z_dim, in_channel=in_channel).to(device)
     set_precision(vae, precision)
     optimizer = torch.optim.Adam(vae.parameters(), lr=vae_lr)
     hyperparameter = {"temperature": temperature, "alpha": alpha, "beta": beta, "ps": ps, "loc": 0, "scale": 1}
     if loss_name != "snn_loss":
         hyperparameter["loss_name"] = loss_name
+    if loss_step is not None:
+        hyperparameter["loss_step"] = loss_step
     return CLEARVAETrainer(
         vae, optimizer, sim_fn="cosine", hyperparameter=hyperparameter,
         verbose_period=verbose_period, device=device,

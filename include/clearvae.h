@@ -500,6 +500,24 @@ int    cv_supcon_supported(int n, int d, int sim);
 /* floats of the stats workspace for batch n (linear in n) */
 size_t cv_supcon_stats_floats(int n);
 int    cv_supcon(const cv_supcon_args* a, int phase, cv_stream_t stream);   /* 0: rows + loss, 1: gradients */
+/* The step form (the fused CLEAR step's contrastive terms, trainer.py:456-480 with losses.py:98-126, 140-170): up to
+ * two branches on the same labels, n, d, sim, kind and temperature, both in the same launches (the branch is a grid
+ * dimension): phase 0 is two launches (row statistics, loss fold), phase 1 one.  Per branch the semantics are
+ * cv_supcon's, quirks included, but phase 1 ADDS gmul * gscale[0] * dloss / d(mu, logvar) onto what dmu / dlogvar hold
+ * (the [n][4d] d(heads) of the step, read and written in place through ld / gld): every element is read and written
+ * by one lane, no atomics, so two runs give the same bits; for cosine / l2 the logvar columns are not touched; with no
+ * kept row the loss is NaN and exactly 0 is added. The branches' stats workspaces and gradient elements
+ * must not overlap.  Same envelope as cv_supcon; no allocation, no synchronisation, capturable. */
+typedef struct cv_supcon_branch {
+  const float* mu; const float* logvar; int ld;   /* rows of stride ld (logvar NULL allowed for cosine / l2) */
+  int ps;
+  float* dmu; float* dlogvar; int gld;            /* phase 1: accumulated into, never overwritten */
+  const float* gscale; float gmul;                /* upstream: gmul * gscale[0] (gscale: [1], device memory) */
+  float* loss_out;                                /* [1], phase 0 */
+  float* stats;                                   /* [cv_supcon_stats_floats(n)] per branch */
+} cv_supcon_branch;
+int    cv_supcon_step(const cv_supcon_branch* br, int nbr, const int64_t* label, int n, int d, int sim, int kind,
+                      float temperature, int phase, cv_stream_t stream);   /* nbr 1 or 2; phase 0 | 1 */
 
 /* ---- MI upper bounds (mi_estimator.py:108-198; CLUB: mi_estimator.py:43-55, VarUB: mi_estimator.py:222-224) ---- */
 enum { CV_MI_NONE = 0, CV_MI_CLUBSAMPLE = 1, CV_MI_L1OUT = 2, CV_MI_CLUB = 3, CV_MI_VARUB = 4,
