@@ -238,6 +238,11 @@ class cv_lam_grad(ctypes.Structure):
     _fields_ = [("w", c_void_p), ("b", c_void_p)]
 
 
+class cv_eval_sink(ctypes.Structure):
+    _fields_ = [("lat_c", c_void_p), ("lat_s", c_void_p), ("label", c_void_p), ("cap", c_int64),
+                ("cursor", c_void_p), ("totals", c_void_p)]
+
+
 _P = POINTER
 # name -> (restype, argtypes)
 class cv_conv_pack(ctypes.Structure):
@@ -489,6 +494,12 @@ _SIGS = {
         c_int,
         [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p],
+    ),
+    "cv_eval_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cv_eval_batch": (
+        c_int,
+        [_P(cv_bn), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, _P(c_void_p),
+         _P(c_float), c_int, _P(cv_eval_sink), c_void_p, c_void_p],
     ),
     "cv_tsne_workspace_bytes": (c_size_t, [c_int]),
     "cv_tsne_affinity": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),

@@ -759,7 +759,8 @@ class Workspace:
                         output: str = "xhat", rec_scale=None) -> Program:
         """Encoder + heads + reparam + decoder (+ running statistics).  output: 'xhat'
         (cv_output_forward), 'loss' (cv_convt_output_loss: the last ConvT + cv_output_loss with the backward seed),
-        'none' (statistics only)."""
+        'none' (train: statistics only; eval: the pre-BN output stays in y_dec[-1] and xhat is not written, the form
+        cv_eval_batch reads: cvhip/evaluate.py)."""
         P = Program()
         if train:
             P.add("cv_zero", self.stats, self.stats.numel() * 8)
@@ -923,6 +924,8 @@ class Workspace:
                 if q is not None:
                     P.add("cv_ntxent_aux_flush")
                 return
+            # (output 'none' in eval mode: the last ConvTranspose2d writes y_dec[-1] as usual and no cv_output_forward
+            # follows: cv_eval_batch computes the reconstruction term from it without materialising xhat)
             # (a train-mode forward whose output is not wanted: the last ConvTranspose2d writes only its BatchNorm's
             # batch statistics, not the pre-BN image — cv_conv_forward with out = NULL, the edge scatter)
             stats_only = output == "none" and train and li == len(sp.dec) - 1 and self.STATS_ONLY_OUT

@@ -101,26 +101,100 @@ def _batch(batch, device, transform):
 # ----------------------------------------------------------------------------- CLEAR-VAE
 
 
-class _ClearEval:
+EVAL_BACKENDS = ("module", "fused")  # evaluate(backend=...) / CVHIP_EVAL of the VAE trainers
+
+
+def _eval_backend(backend) -> str:
+    """"module" or "fused": the argument, else the environment variable CVHIP_EVAL (read at the call, so the
+    reference scripts switch without an edit), else "module"."""
+    if backend is None:
+        backend = os.environ.get("CVHIP_EVAL") or "module"
+    if backend not in EVAL_BACKENDS:
+        raise ValueError(f"evaluate: backend / CVHIP_EVAL must be one of {EVAL_BACKENDS}, not {backend!r}")
+    return backend
+
+
+class _FusedEval:
+    """The fused evaluate() of the VAE trainers (cvhip.evaluate.EvalPass: each validation batch one replayed HIP
+    graph, the epoch's sums and latents on the device, one host read at the end)."""
+
+    _eval_pass = None
+    _eval_warned = False
+
+    def _eval_pass_for(self, mode, dataloader, why=None):
+        """(pass, capacity), or (None, None) after warning once with the reason: the caller runs "module"."""
+        from cvhip.evaluate import EvalPass
+
+        cap = None
+        if why is None:
+            try:
+                cap = len(dataloader.dataset)
+            except (AttributeError, TypeError):
+                why = "the loader has no dataset with a length (the epoch's capacity)"
+        if why is None:
+            ep = self._eval_pass
+            if ep is None or ep.mode != mode or not ep.compatible():
+                why = EvalPass.unsupported_reason(self, mode)
+                ep = self._eval_pass = None if why is not None else EvalPass.build(self, mode)
+            if ep is not None:
+                return ep, cap
+        if not self._eval_warned:
+            self._eval_warned = True
+            warnings.warn(f"{type(self).__name__}.evaluate(backend='fused') runs as 'module': {why}", stacklevel=3)
+        return None, None
+
+    def _evaluate_fused(self, ep, cap, dataloader, verbose, epoch_id, names, module_batch):
+        """module_batch(X, label) -> (values, z): the module path's values of a batch the pass refuses (one sample,
+        another image shape)."""
+        ep.begin(cap)
+        with torch.no_grad():
+            for batch in tqdm(dataloader, disable=not verbose, desc=f"val-epoch {epoch_id}"):
+                X, label = _batch(batch, self.device, None)
+                if ep.accepts(X):
+                    ep.batch(X, label)
+                else:
+                    values, z = module_batch(X, label)
+                    ep.add_module_batch(values, z, label)
+        totals, _, labels, lat_c, lat_s = ep.finish()
+        mig = mutual_info_gap(labels, lat_c, lat_s)
+        nb = len(dataloader)
+        mse = float(totals[0] / nb)
+        if verbose:
+            print(", ".join("val_" + nm + "={:.3f}" for nm in names).format(*[t / nb for t in totals[:len(names)]]))
+        return mig, mse
+
+
+class _ClearEval(_FusedEval):
     """evaluate() shared by the CLEAR trainers (trainer.py:495-570, 899-965): eval-mode forward on the
     HIP path under no_grad, the same losses, gMIG by mutual_info_gap (sklearn on the CPU as in the reference, or
-    the device kernel with CVHIP_GMIG=device)."""
+    the device kernel with CVHIP_GMIG=device).  backend "fused" (or CVHIP_EVAL=fused) runs the same epoch through
+    cvhip.evaluate.EvalPass; a setup outside its contract warns once and runs "module"."""
 
-    def _evaluate(self, dataloader, verbose, epoch_id, last_name, last_fn):
+    def _module_batch(self, X, label, last_fn):
+        vae, hp = self.model, self.hyperparameter
+        X_hat, lp, z = vae(X, explicit=True)
+        rec, kl_c, kl_s = vae_loss(X_hat, X, **lp)
+        c_loss = contrastive_loss(mu=lp["mu_c"], logvar=lp["logvar_c"], label=label, sim_fn=self.sim_fn,
+                                  temperature=hp["temperature"], **getattr(self, "_loss_kw", {}))
+        last = last_fn(lp, label, z)
+        return (rec, kl_c, kl_s, c_loss, last), z
+
+    def _evaluate(self, dataloader, verbose, epoch_id, last_name, last_fn, backend="module", mode=None):
         vae = self.model
         vae.eval()
-        hp = self.hyperparameter
+        if backend == "fused":
+            ep, cap = self._eval_pass_for(mode, dataloader)
+            if ep is not None:
+                return self._evaluate_fused(ep, cap, dataloader, verbose, epoch_id,
+                                            ("recontr_loss", "kl_c", "kl_s", "c_loss", last_name),
+                                            lambda X, label: self._module_batch(X, label, last_fn))
         totals = [0.0] * 5
         labels, lat_c, lat_s = [], [], []
         with torch.no_grad():
             for batch in tqdm(dataloader, disable=not verbose, desc=f"val-epoch {epoch_id}"):
                 X, label = _batch(batch, self.device, self.transform)
-                X_hat, lp, z = vae(X, explicit=True)
-                rec, kl_c, kl_s = vae_loss(X_hat, X, **lp)
-                c_loss = contrastive_loss(mu=lp["mu_c"], logvar=lp["logvar_c"], label=label, sim_fn=self.sim_fn,
-                                          temperature=hp["temperature"], **getattr(self, "_loss_kw", {}))
-                last = last_fn(lp, label, z)
-                for i, v in enumerate((rec, kl_c, kl_s, c_loss, last)):
+                values, z = self._module_batch(X, label, last_fn)
+                for i, v in enumerate(values):
                     totals[i] += v
                 labels.append(label)
                 lat_c.append(z[:, : vae.z_dim])
@@ -231,7 +305,8 @@ class CLEARVAETrainer(VAETrainer, _ClearEval):
         if engine is not None:
             engine.sync_host_state()
 
-    def evaluate(self, dataloader, verbose, epoch_id):
+    def evaluate(self, dataloader, verbose, epoch_id, backend=None):
+        backend = _eval_backend(backend)
         hp = self.hyperparameter
 
         def s_term(lp, label, z):
@@ -239,7 +314,7 @@ class CLEARVAETrainer(VAETrainer, _ClearEval):
                                  temperature=hp["temperature"], ps=hp["ps"], **self._loss_kw)
             return s if hp["ps"] else -s
 
-        return self._evaluate(dataloader, verbose, epoch_id, "s_loss", s_term)
+        return self._evaluate(dataloader, verbose, epoch_id, "s_loss", s_term, backend, "clear")
 
 
 # ----------------------------------------------------------------------------- CLEAR-MIM
@@ -335,14 +410,15 @@ class ClearMIMVAETrainer(VAETrainer, _ClearEval):
             mi_losses.extend(mis)
             mi_learning_losses.extend(lls)
 
-    def evaluate(self, dataloader, verbose, epoch_id):
+    def evaluate(self, dataloader, verbose, epoch_id, backend=None):
+        backend = _eval_backend(backend)
         est = self.mi_estimator
         est.eval()
 
         def mi_term(lp, label, z):
             return est(z[:, : self.model.z_dim], z[:, self.model.z_dim:])
 
-        return self._evaluate(dataloader, verbose, epoch_id, "mi_loss", mi_term)
+        return self._evaluate(dataloader, verbose, epoch_id, "mi_loss", mi_term, backend, "mim")
 
 
 # ----------------------------------------------------------------------------- outside the hot path
@@ -636,7 +712,7 @@ class LAMCNNTrainer(SimpleCNNTrainer):
         engine.sync_host_state()
 
 
-class HierarchicalVAETrainer(VAETrainer):
+class HierarchicalVAETrainer(VAETrainer, _FusedEval):
     """GVAE / ML-VAE baselines (trainer.py:291-412).  Each step runs as one fused HIP program
     (cvhip.engine.ClearStep, mode "group"): the group evidence of vae.py:159-223 segmented by label on the
     device (cv_group_forward / cv_group_backward), kl_c over the groups and the B/m adjustment of rec and
@@ -714,9 +790,23 @@ class HierarchicalVAETrainer(VAETrainer):
             mig, mse = self.evaluate(dataloader, verbose, epoch_id, with_evidence_acc)
             print(f"gMIG: {round(mig, 3)}; mse: {round(float(mse), 3)}")
 
-    def evaluate(self, dataloader, verbose, epoch_id, with_evidence_acc=False):
+    def evaluate(self, dataloader, verbose, epoch_id, with_evidence_acc=False, backend=None):
+        """backend "fused" (or CVHIP_EVAL=fused): the epoch through cvhip.evaluate.EvalPass (mode "group"), without
+        the group evidence; with_evidence_acc=True, or a setup outside the pass's contract, warns once and runs
+        "module"."""
+        backend = _eval_backend(backend)
         vae = self.model
         vae.eval()
+        if backend == "fused":
+            why = "with_evidence_acc=True needs the group evidence in the pass" if with_evidence_acc else None
+            ep, cap = self._eval_pass_for("group", dataloader, why)
+            if ep is not None:
+                def module_batch(X, label):
+                    X_hat, lp, z = vae(X, explicit=True)
+                    return tuple(vae_loss(X_hat, X, **lp)), z
+
+                return self._evaluate_fused(ep, cap, dataloader, verbose, epoch_id, ("recontr_loss", "kl_c", "kl_s"),
+                                            module_batch)
         tot = [0.0, 0.0, 0.0]
         labels, lat_c, lat_s = [], [], []
         with torch.no_grad():
@@ -845,11 +935,12 @@ class ClearTCVAETrainer(VAETrainer, _ClearEval):
         if log:
             factor_d_losses.extend(torch.cat([t.reshape(1) for t in log]).tolist())
 
-    def evaluate(self, dataloader, verbose, epoch_id):
+    def evaluate(self, dataloader, verbose, epoch_id, backend=None):
+        backend = _eval_backend(backend)
         self.factor_cls.eval()
 
         def mi_term(lp, label, z):
             d = self.factor_cls(z)
             return F.relu(torch.log(d / (1 - d))).mean()
 
-        return self._evaluate(dataloader, verbose, epoch_id, "mi_loss", mi_term)
+        return self._evaluate(dataloader, verbose, epoch_id, "mi_loss", mi_term, backend, "tc")

@@ -704,6 +704,39 @@ int cv_rank_auc(const float* score, int lds, int n, int c, const int32_t* label,
                 const int32_t* start, uint32_t* counts_out, double* ap_sum_out, unsigned long long* u2_out, void* work,
                 cv_stream_t stream);
 
+/* ---- the tail of one evaluate() batch (trainer.py:495-570 for the CLEAR trainers, :366-412 for the GVAE / ML-VAE
+ * one; the terms are vae_loss's, losses.py:41-50) ----
+ * The accumulators of one evaluation epoch, all in device memory: the batches' latents and labels in call order
+ * (what trainer.py:531-541 / :390-396 collect in Python lists and torch.cat) and the running sums of the printed
+ * values (trainer.py:524-530, 548-560). */
+typedef struct cv_eval_sink {
+  float* lat_c; float* lat_s;   /* [cap][d] each                                                   */
+  int64_t* label;               /* [cap]                                                           */
+  int64_t cap;                  /* rows of the three buffers                                       */
+  int64_t* cursor;              /* [2]: rows appended so far, sticky overflow flag                 */
+  double* totals;               /* [8]: rec, kl_c, kl_s, term 0, term 1, (5, 6 unused), batches    */
+} cv_eval_sink;
+/* bytes of cv_eval_batch's `work` for a batch of n images of c channels and hw pixels (three fp64 partials per
+ * workgroup of the element pass; need not be zeroed); 0 for a shape cv_eval_batch refuses */
+size_t cv_eval_workspace_bytes(int n, int c, int hw);
+/* One batch (trainer.py:517-541, losses.py:41-50), from what the eval-mode forward left on the device:
+ *   rec  = mean_n sum_chw (sigmoid(BN(y)) - x)^2 with y the last ConvTranspose2d's pre-BN output, NHWC [n][hw][c] (the
+ *          layout cv_output_forward takes), bn its BatchNorm (eval mode: the running statistics) and x the NCHW
+ *          input; every element's value is cv_output_forward's, xhat itself is not written.  1 <= c <= 4.
+ *   kl_c, kl_s = -0.5 mean_n sum_d (1 + lv - mu^2 - exp(lv)) over the heads [n][4d] = mu_c | lv_c | mu_s | lv_s.
+ *   append: z[:, :d] -> lat_c, z[:, d:] -> lat_s, label -> label, at rows cursor[0] .. cursor[0] + n.
+ *   totals[0..2] += rec, kl_c, kl_s; totals[3 + k] += term_scale[k] * terms[k][0] for k < nterm <= 2 (terms: a host
+ *          array of device scalars written earlier on the stream, e.g. the contrastive and MI losses; term_scale: a
+ *          host array read at the call); totals[7] += 1; cursor[0] += n.
+ * The cursor lives on the device and the kernels advance it, so one captured graph serves every batch of its size.
+ * A batch whose rows do not all fit under cap (or any batch once the flag is set) appends nothing, leaves totals and
+ * cursor[0] as they are and sets cursor[1] = 1; nothing is written at or beyond row cap.
+ * Two launches on the stream (the element pass writes fp64 partials into indexed slots of `work`, the finish pass adds
+ * them in a fixed order): no atomics and no grid-wide wait; two runs from equal state give equal bits. */
+int cv_eval_batch(const cv_bn* bn, const float* y, const float* x, int n, int c, int hw, const float* heads,
+                  const float* z, int d, const int64_t* label, const float* const* terms, const float* term_scale,
+                  int nterm, const cv_eval_sink* sink, double* work, cv_stream_t stream);
+
 /* ---- exact t-SNE for the latent plots (the demo notebooks and expr/visual_utils.py:144-183 call sklearn's
  * TSNE(n_components=2, perplexity=30, learning_rate=200, init='pca').fit_transform on host copies of mu_c and mu_s);
  * sklearn's method="exact" (manifold/_t_sne.py, _utils.pyx), matrix-free: O(n d) memory, no n x n array ----
